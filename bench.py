@@ -6,16 +6,22 @@ N_in = 2M rows, N_out ~= 1.1M rows.  At N GPUs (one process per GPU, launched by
 torch.distributed.run) every rank joins its own key-hash range shard of an N x 1M-key
 key space (weak scaling); there is no collective in the data path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Rank 0 prints ONE JSON line.  `value` = Σ input rows over all ranks x K / the max
 over ranks of the timed region.  `roofline` prices the join kernel (one launch per
 step: rows + context union) by its algorithmic bytes 36·(N_in + N_out) + 12·(|c_a| +
 |c_b| + |c_out|) over its average duration from HIP events on the engine stream.
-`cpu_baseline` times the C restatement (oracle/deltaref.c) on the same config-2
+
+A plain run sets up, settles and warms up, times the K steps and prints the line.
+`--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+Everything else runs only with `--full`: the per-step event pass, the secondary
+configurations (`merkle`: the config-4 anti-entropy round; `changes`, `end_to_end`,
+`config3`, `config5`, `read_runs32`, `mutate`, `anti_entropy_hops`) and
+`cpu_baseline`, which times the C restatement (oracle/deltaref.c) on the same config-2
 inputs on all host cores (OpenMP over key shards, oracle/deltaref_mt.c) and on one core,
-~6 s each.  A secondary Merkle hash+diff rate (config-4
-shape, 1M keys, 1 % differing) is reported under `merkle`.
+~6 s each.  `--no-cpu-baseline`, `--no-merkle` and `--no-configs` leave parts of
+`--full` out.
 """
 from __future__ import annotations
 
@@ -181,6 +187,9 @@ def config4_round(eng, torch, dev, rank=0, world=1, keys_per_rank=12_500_000, st
         lb()
     ev1.record(eng.stream)
     eng.sync()
+    # (dg_engine_sync returns when the stream's work is done, which can be before the
+    # runtime has marked the events complete: wait for the later one itself)
+    ev1.synchronize()
     build_us = ev0.elapsed_time(ev1) * 1e3 / (2 * steps)
     rows = (sa.n + sb.n) / 2
     nb = 1 << depth
@@ -200,6 +209,7 @@ def config4_round(eng, torch, dev, rank=0, world=1, keys_per_rank=12_500_000, st
         ld()
     ev1.record(eng.stream)
     eng.sync()
+    ev1.synchronize()
     diff_us = ev0.elapsed_time(ev1) * 1e3 / steps
 
     # the round as CausalCrdt runs it on the receiving replica: update_state_with_delta
@@ -707,6 +717,7 @@ def config5_rate(eng, torch, dev, rank=0, world=1, n_keys=12_500_000, reps=5, st
         launch()
     ev1.record(eng.stream)
     eng.sync()
+    ev1.synchronize()  # (as in config4_round)
     tk = ev0.elapsed_time(ev1) * 1e-3 / steps
     # the per-launch timeline of the same back-to-back loop: an event between every two
     # launches (config 5 reproducible without a profiler in the process)
@@ -716,6 +727,7 @@ def config5_rate(eng, torch, dev, rank=0, world=1, n_keys=12_500_000, reps=5, st
         launch()
         evs[i + 1].record(eng.stream)
     eng.sync()
+    evs[steps].synchronize()
     per_launch = [evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(steps)]
     out.n = int(d_counts[0].item())
     octx.n = int(d_counts[1].item())
@@ -838,6 +850,49 @@ def mutate_cpu_baseline(sizes=(1000, 10_000), reps=300):
     return {f"keys_{n}": _run_json([exe, str(n), str(reps)]) for n in sizes}
 
 
+DUMP_ROWS = 400_000  # rows sampled over all ranks: 72 B per row as float64 -> ~29 MB
+
+
+def _halves(x):
+    """A 64-bit integer column as float64 [n, 2]: its high and low 32 bits, each exact."""
+    x = np.ascontiguousarray(x).view(np.uint64)
+    return np.stack([x >> np.uint64(32), x & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+
+
+def _piece_sums(x):
+    """Σ over the whole column of each of its 16-bit pieces (low first), exact in float64."""
+    x = np.ascontiguousarray(x).astype(np.uint64)
+    return [float(((x >> np.uint64(s)) & np.uint64(0xFFFF)).sum(dtype=np.uint64)) for s in (0, 16, 32, 48)]
+
+
+def dump_outputs(d, pr, rank, world):
+    """Write what the timed path's last step computed -- the joined store and context of
+    the replica pair `pr`, as a caller of dg_join2_async receives them -- to d/<name>.npy
+    in float64.  64-bit columns are stored as their two 32-bit halves ([n, 2]: high, low),
+    so every value is exact.  The context is written whole; of the rows a fixed sample
+    (seeded by nothing but the row count, indices in rows_index) plus, over ALL rows, the
+    sums of each column's 16-bit pieces (rows_checksum [5, 4]: key, val, ts, node, cnt),
+    which are exact too.  At N ranks each rank's files are prefixed rank<r>_."""
+    os.makedirs(d, exist_ok=True)
+    out, octx = pr["out"], pr["octx"]
+    n, n_ctx = int(pr["d"][0].item()), int(pr["d"][1].item())
+    kind = int(pr["launch"].out_ctx_abi.kind)  # the dg_context the launch writes
+    cols = [getattr(out, f)[:n].cpu().numpy() for f in ("key", "val", "ts", "node", "cnt")]
+    cols = [c.view(np.uint32 if c.dtype.itemsize == 4 else np.uint64) for c in cols]
+    cap = max(DUMP_ROWS // max(world, 1), 1)
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    pre = os.path.join(d, f"rank{rank}_" if world > 1 else "")
+    np.save(pre + "counts.npy", np.array([n, n_ctx, kind], dtype=np.float64))
+    np.save(pre + "rows_index.npy", idx.astype(np.float64))
+    np.save(pre + "rows_checksum.npy", np.array([_piece_sums(c) for c in cols], dtype=np.float64))
+    for f, c in zip(("key", "val", "ts", "node", "cnt"), cols):
+        c = c[idx]
+        np.save(pre + f"rows_{f}.npy",
+                c.astype(np.float64) if f == "node" else _halves(c))
+    np.save(pre + "ctx_node.npy", octx.node[:n_ctx].cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(pre + "ctx_cnt.npy", _halves(octx.cnt[:n_ctx].cpu().numpy()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -845,10 +900,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--settle-ms", type=float, default=300.0,
                     help="untimed joins for this long before the warm-up steps (clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-merkle", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's joined store and "
+                         "context to DIR/<name>.npy (float64, see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the per-step event pass, the secondary "
+                         "configurations and the CPU baselines (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-merkle", action="store_true",
+                    help="with --full: skip the config-4 anti-entropy round")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the secondary config-3 / config-5 measurements")
+                    help="with --full: skip the other secondary measurements (config 3, config 5, ...)")
     ap.add_argument("--rotate", type=int, default=4,
                     help="distinct replica pairs joined round-robin (defeats cache residency)")
     ap.add_argument("--calibrate", action="store_true",
@@ -948,18 +1011,23 @@ def main():
     if world > 1:
         dist.barrier()
 
-    # per-step event pairs in a separate pass (each pair adds its own record latency, so
-    # this median is an upper bound; reported for reference)
-    nev = min(args.steps, 100)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(nev + 1)]
-    with torch.cuda.stream(stream):
-        for i in range(nev):
-            ev[i].record(stream)
-            launches[i % R]()
-        ev[nev].record(stream)
-    eng.sync()
-    torch.cuda.synchronize()
-    step_event_median_us = float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(nev)])) * 1e3
+    if args.dump_outputs and args.steps > 0:  # the pair the last timed step joined
+        dump_outputs(args.dump_outputs, pairs[(args.steps - 1) % R], rank, world)
+
+    step_event_median_us = None
+    if args.full:
+        # per-step event pairs in a separate pass (each pair adds its own record latency, so
+        # this median is an upper bound; reported for reference)
+        nev = min(args.steps, 100)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(nev + 1)]
+        with torch.cuda.stream(stream):
+            for i in range(nev):
+                ev[i].record(stream)
+                launches[i % R]()
+            ev[nev].record(stream)
+        eng.sync()
+        torch.cuda.synchronize()
+        step_event_median_us = float(np.median([ev[i].elapsed_time(ev[i + 1]) for i in range(nev)])) * 1e3
 
     calib_rows = 0
     if args.calibrate:
@@ -990,6 +1058,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": el_max / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1022,7 +1091,7 @@ def main():
                 "launch_timing": "HIP events on the engine stream from the end of the timed "
                                  "region's first step to the end of its last, / (steps - 1)",
                 "host_submit_us_per_step": host_submit_s / args.steps * 1e6,
-                "per_step_event_median_us": step_event_median_us,
+                **({"per_step_event_median_us": step_event_median_us} if args.full else {}),
                 "settle": {"ms": args.settle_ms, "joins": n_settle,
                            "note": "untimed joins before the warm-up steps"},
             },
@@ -1043,9 +1112,9 @@ def main():
         return r
 
     secondaries = {}
-    if not args.no_merkle:  # every rank runs its shard's round
+    if args.full and not args.no_merkle:  # every rank runs its shard's round
         secondaries["merkle"] = aggregate(*config4_round(eng, torch, dev, rank, world, cdev=cdev))
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         if world == 1:  # per-GPU secondaries of the config-2 pair: measured at N = 1
             secondaries["changes"] = changes_rate(eng, torch, pairs[0])
             secondaries["end_to_end"] = e2e_rate(eng, torch, pairs[0])
@@ -1061,11 +1130,11 @@ def main():
             secondaries["anti_entropy_hops"] = hop_rate()
     if rank == 0:
         res.update(secondaries)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(a, b)
             if not args.no_configs:
                 res["cpu_baseline"]["mutate"] = mutate_cpu_baseline()
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = None
         import resource
         res["host_peak_rss_gb"] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20  # (KiB)

@@ -406,6 +406,7 @@ class Engine:
 
         # the device memory the raw pointers name stays alive as long as the callable
         launch._keep = (a, ca, b, cb, out, out_ctx, args, keys, d_counts)
+        launch.out_ctx_abi = args[5]  # the dg_context each launch fills in (its kind)
         return launch
 
     def joink(self, stores, ctxs, out: Store | None = None, out_ctx: Context | None = None):

@@ -1,13 +1,15 @@
 # A/B of a library build against the base on the bench's own numbers, alternating:
 #   bash tools/ab_bench.sh <variant .so under ab/> [bench args]
+# Logs go to $DG_OUT/abb (default _out/abb in the repository).
 set -o pipefail
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 V=$1; shift
-mkdir -p $R/gpurun_out/abb
+O=${DG_OUT:-$R/_out}/abb
+mkdir -p $O
 for v in base var base var; do
   if [ $v = var ]; then export DG_LIB_PATH=$R/delta_crdt_ex_amd/ab/$V; else unset DG_LIB_PATH; fi
-  timeout -k 10 300 python -u $R/bench.py --no-cpu-baseline "$@" > $R/gpurun_out/abb/$v.log 2>&1 || { echo FAIL $v; tail -5 $R/gpurun_out/abb/$v.log; exit 1; }
-  python3 - $R/gpurun_out/abb/$v.log $v <<'PY'
+  timeout -k 10 300 python -u $R/bench.py --full --no-cpu-baseline "$@" > $O/$v.log 2>&1 || { echo FAIL $v; tail -5 $O/$v.log; exit 1; }
+  python3 - $O/$v.log $v <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric"')][-1])
 r = d["roofline"]

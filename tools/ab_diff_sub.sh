@@ -2,8 +2,9 @@
 # each passes the diff tests, then bench --no-configs (the diff's back-to-back frac) twice,
 # alternating, then the config-4 round under rocprofv3 (merkle_diff_count_kernel).
 set -o pipefail
-R=$GRAFT_REPO_ROOT; cd $R
-O=$R/gpurun_out/sub; mkdir -p $O
+# Everything goes to $DG_OUT/sub (default _out/sub in the repository).
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
+O=${DG_OUT:-$R/_out}/sub; mkdir -p $O && O=$(cd $O && pwd)
 VARS="intree DG_DIFF_NT1 DG_DIFF_NT2"
 use() { if [ $1 = intree ]; then unset DG_LIB_PATH DG_LIB_ANY_DIGEST; else export DG_LIB_PATH=$R/delta_crdt_ex_amd/ab/libdeltagpu_$1.so DG_LIB_ANY_DIGEST=1; fi; }
 for v in $VARS; do use $v
@@ -11,7 +12,7 @@ for v in $VARS; do use $v
   echo "$v $(tail -1 $O/t_$v.log)"
 done
 for round in 1 2; do for v in $VARS; do use $v
-  timeout -k 10 300 python -u bench.py --no-configs --no-cpu-baseline --steps 20 --warmup 5 > $O/b_$v$round.log 2>&1 || { echo BENCH_FAIL $v; tail -5 $O/b_$v$round.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --no-configs --no-cpu-baseline --steps 20 --warmup 5 > $O/b_$v$round.log 2>&1 || { echo BENCH_FAIL $v; tail -5 $O/b_$v$round.log; exit 1; }
   python3 -c "
 import json,sys
 d=json.loads([l for l in open('$O/b_$v$round.log') if l.startswith('{\"metric\"')][-1]); m=d['merkle']
