@@ -124,6 +124,19 @@ class dg_merkle_cont(C.Structure):
     ]
 
 
+DG_DIFF_OLD = 1
+DG_DIFF_NEW = 2
+
+
+class dg_lww_diffs(C.Structure):
+    _fields_ = [
+        ("old_val", VP),
+        ("new_val", VP),
+        ("flags", VP),
+        ("cap", C.c_uint64),
+    ]
+
+
 class DeltaGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libdeltagpu error {code}: {msg}")
@@ -169,6 +182,13 @@ _SIGS = {
                                     C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
                                     C.POINTER(dg_store), C.c_void_p, P64, C.c_uint64, P64,
                                     C.POINTER(C.c_int), C.POINTER(dg_store), C.POINTER(dg_context)]),
+    "dg_join_delta_diffs": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
+                                      C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
+                                      C.POINTER(dg_store), C.c_void_p, P64, C.c_uint64, P64,
+                                      C.POINTER(C.c_int), C.POINTER(dg_store), C.POINTER(dg_context),
+                                      C.POINTER(dg_lww_diffs)]),
+    "dg_read_diff": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_store), P64, C.c_uint64,
+                               C.POINTER(dg_lww_diffs)]),
     "dg_take_keys": (C.c_int, [C.c_void_p, C.POINTER(dg_store), P64, C.c_uint64,
                                C.POINTER(dg_store)]),
     "dg_mutate_batch": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
@@ -259,13 +279,16 @@ def load(path: str = LIB_PATH):
             f"{path} is missing: build it with `python -m delta_crdt_ex_amd.build` "
             "(libdeltagpu has no CPU fallback)")
     lib = C.CDLL(path)
+    any_digest = os.environ.get("DG_LIB_ANY_DIGEST") == "1"
     for name, (res, args) in _SIGS.items():
+        if any_digest and not hasattr(lib, name):  # (an earlier commit's build lacks newer entry points)
+            continue
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
     built = lib.dg_build_digest().decode()
     # (DG_LIB_ANY_DIGEST=1: an A/B against a build of an earlier commit, tools/build_base.sh)
-    if os.path.isdir(CSRC) and built != source_digest() and os.environ.get("DG_LIB_ANY_DIGEST") != "1":
+    if os.path.isdir(CSRC) and built != source_digest() and not any_digest:
         raise RuntimeError(
             f"{path} is stale: built from sources {built}, the tree's are {source_digest()}; "
             "rebuild with `python -m delta_crdt_ex_amd.build`")

@@ -1,7 +1,9 @@
 """Host mirror of the data path of `DeltaCrdt.CausalCrdt` around the join (reference
 lib/delta_crdt/causal_crdt.ex): applying a delta to a replica's state and the diffs
-its `on_diffs` subscriber receives.  The GenServer, neighbours, sync messages,
-MerkleMap and storage are out of scope.
+its `on_diffs` subscriber receives.  The GenServer, neighbours and sync messages are
+out of scope; the MerkleMap (aw_lww_map.merkle_map, store.MerkleTree,
+DESIGN.md §4.3), the sharded round (sharding.py, §6) and storage (storage.py, §4.6) have
+modules of their own.
 
     from delta_crdt_ex_amd import aw_lww_map as M, causal_crdt as CC
     st = M.compress_dots(M.new())
@@ -10,8 +12,13 @@ MerkleMap and storage are out of scope.
 
 update_state_with_delta/3 (:383-404) runs join/3 and diff/3 (:343-351) as ONE
 libdeltagpu call (dg_join2_changes: the changed keys come out of the join's merge),
-then diffs_to_callback/3 (:359-381) reads the changed keys from the old and the new
-state (dg_read_lww with those keys) and keeps the keys whose read value changed.
+then diffs_to_callback/3 (:359-381) reads the changed keys on the old and on the new
+state in one more (dg_read_diff) and keeps the keys whose read value changed.
+
+update_resident_state_with_delta does the same to a state that stays on the device and
+is joined in place (dg_join_delta_diffs: the join, the changed keys, the MerkleMap update
+and both reads in one call) -- the old rows are overwritten, so the reads before the join
+come out of the join itself.
 """
 from __future__ import annotations
 
@@ -19,7 +26,36 @@ import numpy as np
 import torch
 
 from . import aw_lww_map as M
-from .store import u64
+from ._abi import DG_DIFF_NEW, DG_DIFF_OLD
+from .store import Context, Store, u64
+
+
+def _keyset(U, keys):
+    """`keys` as (key id, key) pairs in the caller's order, and the ascending unique ids on
+    the device (keys by interned id, not Python equality)."""
+    order = [(U.key(k), k) for k in keys]
+    kids = np.array(sorted({kid for kid, _ in order}), dtype=np.uint64)
+    return order, torch.from_numpy(np.ascontiguousarray(kids).view(np.int64)).to(M._dev())
+
+
+def _callback_diffs(U, order, changed, old_val, new_val, flags):
+    """diffs_to_callback/3 (:361-381) from the device's reads of the changed keys: a list of
+    ("add", key, value) / ("remove", key) in `keys` order."""
+    by = {int(k): (int(f), int(o), int(n))
+          for k, o, n, f in zip(u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())}
+    diffs = []
+    for kid, k in order:
+        if kid not in by:
+            continue
+        f, o, n = by[kid]
+        # Map.get(read, key) (:369): nil for an absent key AND for a key whose value is nil
+        o = o if f & DG_DIFF_OLD and U.value_term(o) is not None else None
+        n = n if f & DG_DIFF_NEW and U.value_term(n) is not None else None
+        if o == n:  # {old, old} -> []  (value ids: equal exactly when the terms are =:=)
+            continue
+        # {_old, nil} -> {:remove, key}  (delta_subscriber_test.exs:26-27); else {:add, ...}
+        diffs.append(("remove", k) if n is None else ("add", k, U.value_term(n)))
+    return diffs
 
 
 def update_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys):
@@ -31,46 +67,43 @@ def update_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys):
     the reference's map lookups and `{old, old}` match do, and a nil value reads as an
     absent key (H9)."""
     U = state.universe
-    order = [(U.key(k), k) for k in keys]  # keys by interned id, not Python equality
-    kids = np.array(sorted({kid for kid, _ in order}), dtype=np.uint64)
-    kt = torch.from_numpy(np.ascontiguousarray(kids).view(np.int64)).to(M._dev())
-    out, octx, changed = M.engine().join2_changes(state.rows, state.ctx, delta.rows, delta.ctx,
-                                                  keys=kt)
+    order, kt = _keyset(U, keys)
+    eng = M.engine()
+    out, octx, changed = eng.join2_changes(state.rows, state.ctx, delta.rows, delta.ctx, keys=kt)
     new = M.AWLWWMap(out, octx, U)
     if changed.numel() == 0:
         return new, None
-    ch = set(int(x) for x in u64(changed))
-    ckeys = [(kid, k) for kid, k in order if kid in ch]
-    old_v, new_v = _read_ids(state, ckeys), _read_ids(new, ckeys)
-    diffs = []
-    for kid, k in ckeys:
-        # Map.get(read, key) (:369): nil for an absent key AND for a key whose value is nil
-        o, n = _get(U, old_v, kid), _get(U, new_v, kid)
-        if o == n:  # {old, old} -> []  (value ids: equal exactly when the terms are =:=)
-            continue
-        # {_old, nil} -> {:remove, key}  (delta_subscriber_test.exs:26-27); else {:add, ...}
-        diffs.append(("remove", k) if n is None else ("add", k, U.value_term(n)))
-    return new, diffs
+    old_val, new_val, flags = eng.read_diff(state.rows, out, changed)
+    return new, _callback_diffs(U, order, changed, old_val, new_val, flags)
 
 
-def _get(U, ids, kid):
-    """`Map.get(read_result, key)` as a value id: None stands for nil, which the reference
-    returns both for a key read/2 did not return and for one whose value is the atom nil
-    (causal_crdt.ex:369-372)."""
-    v = ids.get(kid)
-    if v is None or U.value_term(v) is None:
+def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys, spare: Store,
+                                     tree=None):
+    """update_state_with_delta on a state that stays resident: `state` itself becomes the
+    join (its rows in place, or through `spare` when a key's row count changed; its context
+    the union; `tree`, a MerkleTree over its rows, follows) and the same `diffs` value is
+    returned.  Nothing of the old state is kept on the host or read back: the reads before
+    the join come out of the join's own walk of each key (Engine.join_delta_diffs)."""
+    U = state.universe
+    order, kt = _keyset(U, keys)
+    eng = M.engine()
+    rows, ctx = state.rows, state.ctx
+    need = ctx.n + delta.ctx.n
+    if ctx.cap < need:  # room for the union (a resident replica's context grows by doubling)
+        grown = Context.empty(ctx.kind, 2 * need, rows.device)
+        grown.node[: ctx.n].copy_(ctx.node[: ctx.n])
+        grown.cnt[: ctx.n].copy_(ctx.cnt[: ctx.n])
+        ctx.node, ctx.cnt = grown.node, grown.cnt
+    if spare.cap < rows.n + delta.rows.n:
+        grown = Store.empty(2 * (rows.n + delta.rows.n), rows.device)
+        for f in ("key", "val", "ts", "node", "cnt"):
+            setattr(spare, f, getattr(grown, f))
+    changed, old_val, new_val, flags, _ = eng.join_delta_diffs(rows, ctx, delta.rows, delta.ctx, kt,
+                                                               spare, tree)
+    state._host = None
+    if changed.numel() == 0:
         return None
-    return v
-
-
-def _read_ids(state: M.AWLWWMap, ckeys):
-    """read/2 on the device for the (key id, key) pairs: {key id: value id}."""
-    if state.rows.n == 0 or not ckeys:
-        return {}
-    kids = np.array(sorted({kid for kid, _ in ckeys}), dtype=np.uint64)
-    kt = torch.from_numpy(np.ascontiguousarray(kids).view(np.int64)).to(M._dev())
-    ok, ov = M.engine().read_lww(state.rows, keys=kt)
-    return {int(k): int(v) for k, v in zip(u64(ok), u64(ov))}
+    return _callback_diffs(U, order, changed, old_val, new_val, flags)
 
 
 def apply_ops(state: M.AWLWWMap, ops, node_id):
@@ -81,4 +114,4 @@ def apply_ops(state: M.AWLWWMap, ops, node_id):
     return update_state_with_delta(state, delta, keys)
 
 
-__all__ = ["update_state_with_delta", "apply_ops"]
+__all__ = ["update_state_with_delta", "update_resident_state_with_delta", "apply_ops"]

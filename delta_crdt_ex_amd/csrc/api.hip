@@ -945,6 +945,15 @@ static int take_changed_rows(dg_engine* e, const dg_store* src, const uint64_t* 
   return DG_OK;
 }
 
+// dg_join_delta_diffs' output on the paths that do not compute it in the join (the splice, the
+// full join): dg_read_diff of the changed keys.  Like take_changed_rows it runs after the join
+// is committed, so a failure is never the join's error: diffs->cap = 0 says "not written".
+static int gather_diffs(dg_engine* e, const dg_store* olds, const dg_store* news, const uint64_t* changed,
+                        uint64_t n_changed, dg_lww_diffs* diffs) {
+  if (dg_read_diff(e, olds, news, changed, n_changed, diffs) != DG_OK) diffs->cap = 0;
+  return DG_OK;
+}
+
 // dg_join_delta's one-wait path (kdelta.hip): count + scan, the context union, the tree's
 // put/delete and re-reduction, the write (in place, or into `spare` with the moved rows'
 // copy behind it), then ONE publish and wait.  *done = false and nothing changed when the
@@ -953,7 +962,7 @@ static int take_changed_rows(dg_engine* e, const dg_store* src, const uint64_t* 
 static int kd_join_delta(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
                          const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys, dg_store* spare,
                          dg_merkle* tree, uint64_t* changed, uint64_t cap, uint64_t* n_changed, int* swapped,
-                         dg_store* rows, dg_context* ctx_out, bool* done) {
+                         dg_store* rows, dg_context* ctx_out, const dg_lww_diffs* diffs, bool* done) {
   *done = false;
   if (!e->kd || n_keys == 0 || state_ctx->kind != DG_CTX_VV || state->cap < state->n ||
       !pair_aligned(state->key, state->val, state->ts, state->node, state->cnt) ||
@@ -964,7 +973,7 @@ static int kd_join_delta(dg_engine* e, dg_store* state, dg_context* state_ctx, c
   auto al = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t per_key = al(nk * 8), per_key1 = al((nk + 1) * 8), tiles_b = al(ntiles * KD_NV * 8);
   const size_t uc_b = al(uctx_cap * 8) + al(uctx_cap * 4), cu_b = al(ctx_union_tmp_bytes(state_ctx->n, delta_ctx->n));
-  const size_t bytes = 7 * per_key + per_key1 + tiles_b + al((a_tiles + 2) * 8) + uc_b + cu_b;
+  const size_t bytes = (diffs ? 9 : 7) * per_key + per_key1 + tiles_b + al((a_tiles + 2) * 8) + uc_b + cu_b;
   TRY(ensure_buf(e, &e->kdb, &e->kdb_cap, bytes));
   char* q = (char*)e->kdb;
   auto take = [&](size_t b) {
@@ -996,6 +1005,14 @@ static int kd_join_delta(dg_engine* e, dg_store* state, dg_context* state_ctx, c
   u64* uc_cnt = (u64*)take(al(uctx_cap * 8));
   u32* uc_node = (u32*)take(al(uctx_cap * 4));
   void* cu_tmp = take(cu_b);
+  if (diffs) {  // dg_join_delta_diffs: the per-key winners (allocated last and only then)
+    p.has_diffs = 1;
+    p.dv_old = (u64*)take(per_key);
+    p.dv_new = (u64*)take(per_key);
+    p.old_val = diffs->old_val;
+    p.new_val = diffs->new_val;
+    p.dflags = diffs->flags;
+  }
   p.uc_node = uc_node;
   p.uc_cnt = uc_cnt;
   p.ntiles = ntiles;
@@ -1113,7 +1130,8 @@ static int kd_join_delta(dg_engine* e, dg_store* state, dg_context* state_ctx, c
 static int join_delta_core(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
                            const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
                            dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
-                           uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out, bool* kd_done) {
+                           uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out, bool* kd_done,
+                           dg_lww_diffs* diffs = nullptr) {
   if (!e) return fail(DG_E_INVAL, "null engine");
   if (!swapped || !n_changed || (cap && !changed) || !spare || !state || !state_ctx)
     return fail(DG_E_INVAL, "dg_join_delta: null argument");
@@ -1143,7 +1161,7 @@ static int join_delta_core(dg_engine* e, dg_store* state, dg_context* state_ctx,
   {
     bool done = false;
     TRY(kd_join_delta(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, changed, cap,
-                      n_changed, swapped, rows, ctx_out, &done));
+                      n_changed, swapped, rows, ctx_out, diffs, &done));
     *kd_done = done;
     if (done) return DG_OK;
   }
@@ -1171,6 +1189,8 @@ static int join_delta_core(dg_engine* e, dg_store* state, dg_context* state_ctx,
     std::swap(*state, *spare);
     *swapped = 1;
     if (rows) TRY(take_changed_rows(e, state, changed, *n_changed, rows));  // (the new state)
+    // (the old rows are still where they were: the join wrote the spare store)
+    if (diffs) TRY(gather_diffs(e, &old_state, state, changed, *n_changed, diffs));
     return DG_OK;
   }
   TRY(splice_edit(e, &w, state_ctx, delta, delta_ctx, keys, n_keys, &w.uctx, true, changed, cap));
@@ -1231,6 +1251,9 @@ static int join_delta_core(dg_engine* e, dg_store* state, dg_context* state_ctx,
   // the changed keys' rows from the edit (a changed key is a keyset key: all of its
   // joined rows are in the edit), not by a search of the state
   if (rows) TRY(take_changed_rows(e, &ed, changed, *n_changed, rows));
+  // ... and their reads before and after from the taken rows and the edit (the same reason;
+  // in place the state's own old rows are overwritten by now)
+  if (diffs) TRY(gather_diffs(e, &w.ak, &ed, changed, *n_changed, diffs));
   return DG_OK;
 }
 
@@ -1375,10 +1398,11 @@ int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, con
 static int join_delta_impl(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
                            const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
                            dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
-                           uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out = nullptr) {
+                           uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out = nullptr,
+                           dg_lww_diffs* diffs = nullptr) {
   bool kd_done = false;
   TRY(join_delta_core(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, changed, cap, n_changed,
-                      swapped, rows, ctx_out, &kd_done));
+                      swapped, rows, ctx_out, &kd_done, diffs));
   if (ctx_out && !kd_done) {  // (the other paths: the context copied after the join)
     ctx_out->n = state_ctx->n;
     ctx_out->kind = state_ctx->kind;
@@ -1415,6 +1439,42 @@ int dg_join_delta_out(dg_engine* e, dg_store* state, dg_context* state_ctx, cons
   if (!rows || !ctx_out) return fail(DG_E_INVAL, "dg_join_delta_out: null rows or ctx_out");
   return join_delta_impl(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, changed,
                          cap, n_changed, swapped, rows, ctx_out);
+}
+
+static_assert(KD_DIFF_OLD == DG_DIFF_OLD && KD_DIFF_NEW == DG_DIFF_NEW, "deltagpu.h's flags are the kernels'");
+
+int dg_read_diff(dg_engine* e, const dg_store* old_s, const dg_store* new_s, const uint64_t* keys,
+                 uint64_t n_keys, dg_lww_diffs* out) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_store(old_s, "dg_read_diff old"));
+  TRY(check_store(new_s, "dg_read_diff new"));
+  if (!out) return fail(DG_E_INVAL, "dg_read_diff: null output");
+  if (keys == nullptr && n_keys != 0) return fail(DG_E_INVAL, "dg_read_diff: keys NULL with n_keys>0");
+  if (out->cap < n_keys)
+    return fail(DG_E_CAPACITY, "dg_read_diff: cap %llu < %llu keys", (unsigned long long)out->cap,
+                (unsigned long long)n_keys);
+  if (n_keys && (!out->old_val || !out->new_val || !out->flags)) return fail(DG_E_INVAL, "dg_read_diff: null output array");
+  if (n_keys == 0) return DG_OK;
+  TRY(set_device(e));
+  TRY(settle(e));
+  HIP_TRY(launch_read_diff(rows_of(old_s), rows_of(new_s), keys, n_keys, out->old_val, out->new_val, out->flags,
+                           e->stream));
+  return read_counts(e, 0);
+}
+
+int dg_join_delta_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                        const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                        dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
+                        uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out,
+                        dg_lww_diffs* diffs) {
+  if (!diffs) return fail(DG_E_INVAL, "dg_join_delta_diffs: null diffs");
+  if (diffs->cap < cap)
+    return fail(DG_E_INVAL, "dg_join_delta_diffs: diffs cap %llu < changed cap %llu",
+                (unsigned long long)diffs->cap, (unsigned long long)cap);
+  if (cap && (!diffs->old_val || !diffs->new_val || !diffs->flags))
+    return fail(DG_E_INVAL, "dg_join_delta_diffs: null diffs array");
+  return join_delta_impl(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, changed,
+                         cap, n_changed, swapped, rows, ctx_out, diffs);
 }
 
 }  // extern "C"

@@ -158,7 +158,14 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
       if (j < nd) rb = load_row(p.d, d_lo + j);
     }
   }
-  if (chg && c_off < p.cap) p.changed[c_off] = k;
+  if (chg && c_off < p.cap) {
+    p.changed[c_off] = k;
+    if (p.has_diffs) {  // (uniform) read/1 of the key before and after, from the count kernel's walk
+      p.old_val[c_off] = p.dv_old[u];
+      p.new_val[c_off] = p.dv_new[u];
+      p.dflags[c_off] = (uint8_t)((na ? KD_DIFF_OLD : 0u) | (ne ? KD_DIFF_NEW : 0u));
+    }
+  }
 }
 
 }  // namespace

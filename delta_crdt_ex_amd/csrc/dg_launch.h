@@ -246,6 +246,11 @@ inline u64 seg_tiles(u64 n) { return (n + SEG_TILE - 1) / SEG_TILE; }
 // scratch: 2 * seg_tiles(n) u64 (per-tile counts and offsets).
 hipError_t launch_read_lww(const Rows& s, const u64* keys, u64 n_keys, u64* out_key, u64* out_val,
                            u64* scratch, u64* d_count, hipStream_t st);
+// read/2 of keys[0, n) (any order, repeats allowed) on two stores side by side
+// (read_diff_kernel): old_val / new_val [i] = the value id keys[i] reads in a / b (absent: 0),
+// flags[i] = KD_DIFF_OLD | KD_DIFF_NEW presence bits.  Either store may be empty.
+hipError_t launch_read_diff(const Rows& a, const Rows& b, const u64* keys, u64 n, u64* old_val,
+                            u64* new_val, uint8_t* flags, hipStream_t st);
 // Sortedness check: sets *d_bad to nonzero if rows are not strictly ascending.
 hipError_t launch_store_check(const Rows& s, u32* d_bad, hipStream_t st);
 
@@ -369,8 +374,16 @@ struct KdArgs {
   u32* arrive;         // the count kernel's arrival counter (zero, left zero)
   u32* err;            // the tree update's input-error word, zero on entry (state writes
                        //   skipped when set; the host zeroes it after reporting)
+  // dg_join_delta_diffs (has_diffs; otherwise unused and no store issued): per key (nk) the
+  // value id read/1 gives for its rows before and after the join (no row: 0), and per changed
+  // key (cap, beside `changed`: device or mapped host memory) the two values and KD_DIFF_* flags
+  int has_diffs;
+  u64 *dv_old, *dv_new;
+  u64 *old_val, *new_val;
+  uint8_t* dflags;
 };
-// kd_count_kernel (its last workgroup scans)
+constexpr u32 KD_DIFF_OLD = 1, KD_DIFF_NEW = 2;  // (deltagpu.h DG_DIFF_OLD / DG_DIFF_NEW)
+// kd_count_kernel / kd_count_diffs_kernel (its last workgroup scans)
 hipError_t launch_kd_join(const KdArgs& p, hipStream_t st);
 // kd_finish_kernel (merkle.hip): the write (dg_kdw.h) and, with a tree, its dirty chunks' re-reduction in one launch
 hipError_t launch_kd_finish(const KdArgs& p, const u32* dirty, u32* arrive, u64* hand, const i64* cdelta,

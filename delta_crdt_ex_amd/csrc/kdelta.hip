@@ -20,6 +20,8 @@
 //                     applies: the caller runs the full join), a key run over KD_RUN rows,
 //                     more changed keys than the caller's capacity.  Workgroup 0 of the
 //                     launch computes the context union (Dots.union/2).
+//                     kd_count_diffs_kernel (dg_join_delta_diffs) is the same walk that also
+//                     keeps read/1's winner of the key's rows before and after the join.
 //   kd_finish_kernel  (merkle.hip + dg_kdw.h, one launch) one thread per key: its new rows --
 //                     in place when no key's row count changed, else straight to their
 //                     final places in the spare store -- the changed keys and their rows
@@ -171,7 +173,13 @@ __device__ u64 g_kd_stamps[4096 * 8];
   do {                 \
   } while (0)
 #endif
-__global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
+// DIFFS: the walk also keeps read/1's winner (aw_lww_map.ex:211-224) of the key's rows before
+// and after the join -- a key's rows come in (val, ts) order on both sides and the merge
+// visits them in that order, so "a row wins only on a strictly greater ts" (segred.hip) is
+// one compare per row here -- for dg_join_delta_diffs (causal_crdt.ex:361-381).  Compiled
+// out of kd_count_kernel: the other entry points run the code they ran before.
+template <bool DIFFS>
+__device__ __forceinline__ void kd_count_body(const KdArgs& p) {
   __shared__ u64 tabS[KVT], tabD[KVT];
   __shared__ u64 s_dk[KDL];
   __shared__ u64 s_rng[2];
@@ -215,6 +223,8 @@ __global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
   u32 na = 0, nd = 0, ne = 0;
   bool chg = false, big = false;
   u64 k = 0;
+  u64 ov = 0, nv = 0;    // (DIFFS) the old and the new winner's value id (no row: 0) ...
+  i64 ots = 0, nts = 0;  // ... and ts
   if (u < p.nk) {
     k = p.keys[u];
     key_run(p.a.key, p.a.n, k, a_lo, na);  // the state: an interpolation search
@@ -266,6 +276,14 @@ __global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
         // cover its dot (Dots.member?, :67-73)
         const bool keep = c == 0 || !(dvv ? vv_covers(tabD, p.cd, ra.node, ra.cnt)
                                           : ctx_covers(p.cd.node, p.cd.cnt, p.cd.n, 1, ra.node, ra.cnt));
+        if (DIFFS) {  // (selects, not branches: i == 0 / ne == 0 is "no row so far")
+          const bool wo = (i == 0) | (ra.ts > ots);
+          ots = wo ? ra.ts : ots;
+          ov = wo ? ra.val : ov;
+          const bool wn = keep & ((ne == 0) | (ra.ts > nts));
+          nts = wn ? ra.ts : nts;
+          nv = wn ? ra.val : nv;
+        }
         if (keep) {
           am |= 1ull << i;
           ne++;
@@ -278,6 +296,11 @@ __global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
       } else {
         // the delta's row only: kept unless the state's context covers it
         if (!vv_covers(tabS, p.ca, rb.node, rb.cnt)) {
+          if (DIFFS) {
+            const bool wn = (ne == 0) | (rb.ts > nts);
+            nts = wn ? rb.ts : nts;
+            nv = wn ? rb.val : nv;
+          }
           dm |= 1ull << j;
           ne++;
           chg = true;
@@ -290,6 +313,10 @@ __global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
     p.d_lo[u] = d_lo;
     p.amask[u] = am;
     p.dmask[u] = dm;
+    if (DIFFS) {  // (the write puts them beside the changed keys, dg_kdw.h)
+      p.dv_old[u] = ov;
+      p.dv_new[u] = nv;
+    }
   }
   KDSTAMP(2, 4);
   if (u < p.nk) {  // (a key over KD_RUN: no change recorded, so the undo skips it too)
@@ -388,6 +415,9 @@ __global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) {
   KDSTAMP(0, 7);
 }
 
+__global__ __launch_bounds__(KDB) void kd_count_kernel(KdArgs p) { kd_count_body<false>(p); }
+__global__ __launch_bounds__(KDB) void kd_count_diffs_kernel(KdArgs p) { kd_count_body<true>(p); }
+
 }  // namespace
 
 #ifdef DG_STAMPS
@@ -401,7 +431,11 @@ hipError_t launch_kd_join(const KdArgs& p0, hipStream_t st) {
   KdArgs p = p0;
   p.ntiles = (p.nk + KDB - 1) / KDB;
   if (p.ntiles == 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kd_count_kernel, dim3((unsigned)(p.ntiles + 1)), dim3(KDB), 0, st, p);  // (+ the union's)
+  const dim3 grid((unsigned)(p.ntiles + 1));  // (+ the union's)
+  if (p.has_diffs)
+    hipLaunchKernelGGL(kd_count_diffs_kernel, grid, dim3(KDB), 0, st, p);
+  else
+    hipLaunchKernelGGL(kd_count_kernel, grid, dim3(KDB), 0, st, p);
   return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 //    ({val, ts}, dot), i.e. the flatmap order the BEAM iterates, so "first maximum
 //    in iteration order" (Enum.max_by) == the first row whose ts is strictly
 //    greater than every earlier one.
+//  * read_diff: read/2 of a key list on two stores at once, one thread per key
+//    (dg_read_diff: what diffs_to_callback/3 compares, causal_crdt.ex:361-381).
 //  * store_check: the sorted+unique precondition.
 //
 // Shape: one tile = 1024 rows = 256 threads x 4 consecutive rows; each key run is
@@ -247,6 +249,41 @@ hipError_t launch_seg(SegArgs& p, hipStream_t st) {
   return hipGetLastError();
 }
 
+// read/2 of a key list on two stores side by side (diffs_to_callback/3, causal_crdt.ex:
+// 364-373: the changed keys read on the old and on the new state).  One thread per key: an
+// interpolation search in each store, then a walk of the key's run -- of any length -- with
+// read_lww's rule (a later row wins only on a strictly greater ts).  A few hundred to a few
+// hundred thousand keys against stores of any size: latency-bound by the two search chains.
+constexpr int RDB = 256;
+
+__device__ __forceinline__ bool read_key(const Rows& s, u64 k, u64& val) {
+  u64 i = interp_lower_bound(s.key, 0, s.n, k);
+  i64 ts = 0;
+  bool ok = false;
+  val = 0;
+  for (; i < s.n && s.key[i] == k; i++) {
+    const i64 t = s.ts[i];
+    const u64 v = s.val[i];
+    const bool w = !ok | (t > ts);
+    ts = w ? t : ts;
+    val = w ? v : val;
+    ok = true;
+  }
+  return ok;
+}
+
+__global__ __launch_bounds__(RDB) void read_diff_kernel(Rows a, Rows b, const u64* keys, u64 n, u64* old_val,
+                                                        u64* new_val, uint8_t* flags) {
+  const u64 u = (u64)blockIdx.x * RDB + threadIdx.x;
+  if (u >= n) return;
+  const u64 k = keys[u];
+  u64 ov, nv;
+  const bool oo = read_key(a, k, ov), no = read_key(b, k, nv);
+  old_val[u] = ov;  // (absent: 0, so results compare bit for bit)
+  new_val[u] = nv;
+  flags[u] = (uint8_t)((oo ? KD_DIFF_OLD : 0u) | (no ? KD_DIFF_NEW : 0u));
+}
+
 __global__ void store_check_kernel(Rows s, u32* bad) {
   for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x + 1; i < s.n;
        i += (u64)gridDim.x * blockDim.x) {
@@ -270,6 +307,14 @@ hipError_t launch_read_lww(const Rows& s, const u64* keys, u64 n_keys, u64* out_
   p.d_count = d_count;
   if (p.ntiles == 0) return hipMemsetAsync(d_count, 0, sizeof(u64), st);
   return launch_seg<SegOp::Read>(p, st);
+}
+
+hipError_t launch_read_diff(const Rows& a, const Rows& b, const u64* keys, u64 n, u64* old_val,
+                            u64* new_val, uint8_t* flags, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(read_diff_kernel, dim3((unsigned)((n + RDB - 1) / RDB)), dim3(RDB), 0, st, a, b, keys, n,
+                     old_val, new_val, flags);
+  return hipGetLastError();
 }
 
 hipError_t launch_store_check(const Rows& s, u32* d_bad, hipStream_t st) {

@@ -654,6 +654,88 @@ class Engine:
             tree.store = state
         return changed[: n.value], bool(sw.value)
 
+    def _diffs(self, cap: int):
+        """Device arrays for a dg_lww_diffs of `cap` entries and their struct."""
+        cap = max(int(cap), 1)
+        ov = torch.empty(cap, dtype=_I64, device=self.device)
+        nv = torch.empty(cap, dtype=_I64, device=self.device)
+        fl = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        return ov, nv, fl, _abi.dg_lww_diffs(ov.data_ptr(), nv.data_ptr(), fl.data_ptr(), cap)
+
+    def read_diff(self, old: Store, new: Store, keys: torch.Tensor):
+        """read/2 of `keys` (device int64, any order) on two stores side by side
+        (dg_read_diff; diffs_to_callback/3, causal_crdt.ex:364-373): (old_val, new_val,
+        flags) per key -- value ids (0 where absent) and DG_DIFF_OLD | DG_DIFF_NEW bits."""
+        self._order()
+        n = int(keys.numel())
+        ov, nv, fl, d = self._diffs(n)
+        so, sn = old.abi(), new.abi()
+        kp, nk = self._keys(keys)
+        check(self.lib.dg_read_diff(self.h, C.byref(so), C.byref(sn), kp, nk, C.byref(d)))
+        return ov[:n], nv[:n], fl[:n]
+
+    def join_delta_diffs(self, state: Store, state_ctx: Context, delta: Store, delta_ctx: Context,
+                         keys: torch.Tensor, spare: Store, tree: MerkleTree | None = None,
+                         changed: torch.Tensor | None = None, rows: Store | None = None,
+                         diffs: _abi.dg_lww_diffs | None = None, ctx_out: Context | None = None):
+        """join_delta plus, for every changed key, its LWW read before and after the join
+        (dg_join_delta_diffs: what on_diffs compares, served from the resident state whose
+        old rows the join overwrites).  Returns (changed keys, old_val, new_val, flags,
+        swapped), entry i of the three describing changed[i].  `diffs`: the caller's own
+        arrays (e.g. page-locked memory from dg_host_alloc) receive them instead, and the
+        three returned arrays are None.  `rows` / `ctx_out` (optional): the changed keys'
+        joined rows and a copy of the joined context, as dg_join_delta_out gives them."""
+        self._order()
+        if changed is None:
+            changed = torch.empty(max(int(keys.numel()), 1), dtype=_I64, device=self.device)
+        cap = int(changed.numel())
+        own = diffs is None
+        if own:
+            ov, nv, fl, d = self._diffs(cap)
+        else:
+            ov = nv = fl = None
+            d = diffs
+        ss, sc, sd, cd, sp = state.abi(), state_ctx.abi(), delta.abi(), delta_ctx.abi(), spare.abi()
+        t = tree.abi() if tree is not None else None
+        ro = rows.abi() if rows is not None else None
+        co = ctx_out.abi() if ctx_out is not None else None
+        kp, nk = self._keys(keys)
+        n = C.c_uint64(0)
+        sw = C.c_int(0)
+        check(self.lib.dg_join_delta_diffs(
+            self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp),
+            C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n), C.byref(sw),
+            C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None, C.byref(d)))
+        if rows is not None:
+            rows.n = int(ro.n)
+        if ctx_out is not None:
+            ctx_out.n, ctx_out.kind = int(co.n), int(co.kind)
+        if sw.value:
+            for f in ("key", "val", "ts", "node", "cnt"):
+                a, b = getattr(state, f), getattr(spare, f)
+                setattr(state, f, b)
+                setattr(spare, f, a)
+        state.n = int(ss.n)
+        state_ctx.n = int(sc.n)
+        state_ctx.kind = int(sc.kind)
+        if tree is not None:
+            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
+            tree.store = state
+        nch = int(n.value)
+        if own and d.cap == 0 and nch:
+            # the gather behind a committed join failed (deltagpu.h): the old rows survive
+            # only where the join went through the spare store
+            if not sw.value:
+                raise _abi.DeltaGpuError(_abi.DG_E_DEVICE, "the join applied, but its diffs were not "
+                                         "gathered and the old rows are overwritten")
+            spare.n = int(sp.n)
+            ov, nv, fl = self.read_diff(spare, state, changed[:nch])
+        if sw.value:
+            spare.n = 0
+        if not own:
+            return changed[:nch], None, None, None, bool(sw.value)
+        return changed[:nch], ov[:nch], nv[:nch], fl[:nch], bool(sw.value)
+
     def join_delta_home(self, state: Store, state_ctx: Context, delta: Store, delta_ctx: Context,
                         keys: torch.Tensor, spare: Store, tree: MerkleTree | None = None):
         """dg_join_delta_home: join_delta for a small delta in one launch chain with one

@@ -283,6 +283,51 @@ int dg_join_delta_out(dg_engine* e, dg_store* state, dg_context* state_ctx, cons
                       dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
                       uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out);
 
+/* ---- on_diffs: the LWW read before and after a join ---------------------------- */
+/* What diffs_to_callback/3 (causal_crdt.ex:361-381) compares: read/2 (aw_lww_map.ex:211-224)
+ * of a list of keys on the state before and after a join.  Entry i of the three arrays
+ * describes one key: flags[i] has DG_DIFF_OLD set when the key had a read value before
+ * (old_val[i], a value id) and DG_DIFF_NEW when it has one after (new_val[i]); a value whose
+ * flag is clear is written as 0.  The caller emits {:remove, k} for OLD without NEW,
+ * {:add, k, v} for NEW whose value differs from the old one (or without OLD), nothing for
+ * equal values.  Nil values are the host's matter: the device reports value
+ * ids only.  The arrays (cap entries each) are device memory or memory from dg_host_alloc. */
+#define DG_DIFF_OLD 1 /* the key had a read value before the join */
+#define DG_DIFF_NEW 2 /* it has one after */
+typedef struct dg_lww_diffs {
+  uint64_t* old_val;
+  uint64_t* new_val;
+  uint8_t* flags;
+  uint64_t cap;
+} dg_lww_diffs;
+
+/* read/2 of keys[0, n_keys) (device or dg_host_alloc memory; any order, repeats allowed) on
+ * two stores, side by side (diffs_to_callback, causal_crdt.ex:364-373): entry i describes
+ * keys[i].  Either store may be empty; a key absent from both gives flags 0.
+ * DG_E_CAPACITY when out->cap < n_keys.  Synchronous. */
+int dg_read_diff(dg_engine* e, const dg_store* old_s, const dg_store* new_s, const uint64_t* keys,
+                 uint64_t n_keys, dg_lww_diffs* out);
+
+/* dg_join_delta_out (rows and ctx_out may be NULL here) plus, for changed[i], the LWW read
+ * before and after the join in entry i of `diffs` -- on_diffs served from a resident state,
+ * whose old rows the in-place join overwrites.  DG_E_INVAL, before anything is touched, when
+ * diffs->cap < cap.  A sync delta or a batch of mutations (every delta key in the keyset, at
+ * most 64 rows per key and side) gets them from the per-key join itself: no search or pass
+ * beyond dg_join_delta_out's, and the same ONE host wait.  The other paths gather them with
+ * dg_read_diff after the join is committed -- from the keyset's taken rows and its edit, or
+ * from the old and the joined state.  A failure of that gather is, as for `rows`, not an
+ * error of the join that applied: the call returns DG_OK with diffs->cap set to 0 (the
+ * arrays hold nothing).  When *swapped is 1, *spare still describes the old state's rows
+ * (n included) and dg_read_diff(spare, state, changed, ...) gives them; after an in-place
+ * join the old read is gone and the caller reports the changed keys' new reads.  On an error
+ * return the state, its context and the tree are untouched, as for dg_join_delta, and the
+ * diff arrays are unspecified.  Synchronous. */
+int dg_join_delta_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                        const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                        dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
+                        uint64_t* n_changed, int* swapped, dg_store* rows, dg_context* ctx_out,
+                        dg_lww_diffs* diffs);
+
 /* dg_join_delta_rows for a SMALL delta in ONE launch chain with ONE host wait (the general
  * path waits after each of its four steps): the keyed join, the changed keys, the MerkleMap
  * put/delete + update_hashes, and the results written straight into `home`, host memory
