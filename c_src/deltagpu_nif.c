@@ -845,6 +845,46 @@ static ERL_NIF_TERM merkle_build_nif(ErlNifEnv* env, int argc, const ERL_NIF_TER
   return r;
 }
 
+/* sweep(engine) -> {:ok, %{values: {before, after}, keys: {before, after}}}: the value and
+ * key terms no live state of the engine names any more are dropped from the universe
+ * (dgr_sweep marks on the device, dgm_sweep_values / dgm_sweep_keys drop).  Under the engine
+ * mutex: no delta is between its interning and its join.  State versions do not change. */
+static ERL_NIF_TERM sweep_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  engine_res* g;
+  if (!enif_get_resource(env, argv[0], ENGINE_RT, (void**)&g)) return enif_make_badarg(env);
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  const uint64_t *ids, *hash;
+  const uint8_t* used;
+  uint64_t n, n_used, unknown, dropped;
+  const uint64_t v0 = dgm_value_count(g->u), k0 = dgm_key_count(g->u);
+  dgm_value_hashes(g->u, &ids, &hash, &n);
+  TRY(dgr_sweep(g->r, DG_COL_VAL, ids, n, &used, &n_used, &unknown));
+  if (unknown) TRY(DG_E_INVAL); /* a state holds a value id the table lacks: drop nothing */
+  TRY(dgm_sweep_values(g->u, used, n, &dropped));
+  TRY(dgm_key_ids_sorted(g->u, &ids, &n));
+  TRY(dgr_sweep(g->r, DG_COL_KEY, ids, n, &used, &n_used, &unknown));
+  if (unknown) TRY(DG_E_INVAL);
+  TRY(dgm_sweep_keys(g->u, ids, used, n, &dropped));
+out:;
+  ERL_NIF_TERM r;
+  if (rc) {
+    r = error_term(env, rc);
+  } else {
+    ERL_NIF_TERM m = enif_make_new_map(env);
+    enif_make_map_put(env, m, enif_make_atom(env, "values"),
+                      enif_make_tuple2(env, enif_make_uint64(env, v0),
+                                       enif_make_uint64(env, dgm_value_count(g->u))), &m);
+    enif_make_map_put(env, m, enif_make_atom(env, "keys"),
+                      enif_make_tuple2(env, enif_make_uint64(env, k0),
+                                       enif_make_uint64(env, dgm_key_count(g->u))), &m);
+    r = enif_make_tuple2(env, A_OK, m);
+  }
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
 static ERL_NIF_TERM bytes_term(ErlNifEnv* env, const uint8_t* p, uint64_t n) {
   ERL_NIF_TERM t;
   unsigned char* d = enif_make_new_binary(env, n, &t);
@@ -959,6 +999,7 @@ static ErlNifFunc funcs[] = {
     {"merkle_prepare", 3, merkle_prepare_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_continue", 5, merkle_continue_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"resolve_keys", 2, resolve_keys_nif, 0},
+    {"sweep", 1, sweep_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
 
 ERL_NIF_INIT(Elixir.DeltaCrdt.GPU, funcs, load, NULL, NULL, NULL)

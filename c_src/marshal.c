@@ -190,6 +190,8 @@ struct dgm_universe {
   uint64_t* kid;
   void** kterm;
   uint64_t nk, capk;
+  uint64_t* ksort; /* scratch: the key ids ascending (dgm_key_ids_sorted) */
+  uint64_t capks;
   /* table values (every value but the canonical integers): ascending ids, their terms in
    * the same (map-key) order, their term hashes */
   uint64_t* vid;
@@ -223,6 +225,7 @@ void dgm_universe_free(dgm_universe* u) {
   free(u->kmap.v);
   free(u->kid);
   free(u->kterm);
+  free(u->ksort);
   free(u->vid);
   free(u->vterm);
   free(u->vhash);
@@ -434,6 +437,89 @@ void dgm_last_relabel(const dgm_universe* u, const uint64_t** old_ids, const uin
 }
 
 uint64_t dgm_value_count(const dgm_universe* u) { return u->nv; }
+
+/* ------------------------------------------------------------ sweeps
+ * The tables keep the term of every id they handed out; a sweep drops the entries whose ids
+ * no device store names any more (dg_mark_ids gives the flags).  No id moves: no remap, and
+ * every tree stays valid.  A dropped id may be handed out again to another term. */
+int dgm_sweep_values(dgm_universe* u, const uint8_t* used, uint64_t n, uint64_t* dropped) {
+  if (dropped) *dropped = 0;
+  if (!u || n != u->nv || (n && !used)) return DG_E_INVAL;
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (used[i]) {
+      u->vid[w] = u->vid[i];
+      u->vterm[w] = u->vterm[i];
+      u->vhash[w] = u->vhash[i];
+      w++;
+    } else {
+      u->ops.drop(u->vterm[i], u->ops.ud);
+    }
+  }
+  if (dropped) *dropped = n - w;
+  u->nv = w;
+  return DG_OK;
+}
+
+uint64_t dgm_key_count(const dgm_universe* u) { return u->nk; }
+
+static int cmp_u64(const void* a, const void* b) {
+  const uint64_t x = *(const uint64_t*)a, y = *(const uint64_t*)b;
+  return x < y ? -1 : x > y;
+}
+
+int dgm_key_ids_sorted(dgm_universe* u, const uint64_t** ids, uint64_t* n) {
+  if (!u || !ids || !n) return DG_E_INVAL;
+  int rc = grow((void**)&u->ksort, &u->capks, u->nk ? u->nk : 1, sizeof *u->ksort);
+  if (rc) return rc;
+  if (u->nk) memcpy(u->ksort, u->kid, u->nk * sizeof *u->ksort);
+  qsort(u->ksort, u->nk, sizeof *u->ksort, cmp_u64);
+  *ids = u->ksort;
+  *n = u->nk;
+  return DG_OK;
+}
+
+/* the index of id in ids_sorted[0, n), or n */
+static uint64_t find_u64(const uint64_t* ids_sorted, uint64_t n, uint64_t id) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (ids_sorted[mid] < id)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return (lo < n && ids_sorted[lo] == id) ? lo : n;
+}
+
+int dgm_sweep_keys(dgm_universe* u, const uint64_t* ids_sorted, const uint8_t* used, uint64_t n,
+                   uint64_t* dropped) {
+  if (dropped) *dropped = 0;
+  if (!u || n != u->nk || (n && (!ids_sorted || !used))) return DG_E_INVAL;
+  /* every key must be in the table before anything is dropped */
+  for (uint64_t i = 0; i < n; i++)
+    if (find_u64(ids_sorted, n, u->kid[i]) == n) return DG_E_INVAL;
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (used[find_u64(ids_sorted, n, u->kid[i])]) {
+      u->kid[w] = u->kid[i];
+      u->kterm[w] = u->kterm[i];
+      w++;
+    } else {
+      u->ops.drop(u->kterm[i], u->ops.ud);
+    }
+  }
+  if (dropped) *dropped = n - w;
+  u->nk = w;
+  /* the map names payload indices: rebuilt from the survivors (its capacity stays) */
+  if (u->kmap.cap) memset(u->kmap.h, 0, u->kmap.cap * sizeof *u->kmap.h);
+  u->kmap.n = 0;
+  for (uint64_t i = 0; i < w; i++) {
+    int rc = hmap_put(&u->kmap, nz(u->kid[i]), (uint32_t)i);
+    if (rc) return rc;
+  }
+  return DG_OK;
+}
 
 int dgm_node(dgm_universe* u, const void* term, uint32_t* id) {
   int rc = encode(u, term);

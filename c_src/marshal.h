@@ -105,6 +105,24 @@ void dgm_last_relabel(const dgm_universe* u, const uint64_t** old_ids, const uin
                       uint64_t* n);
 uint64_t dgm_value_count(const dgm_universe* u);
 
+/* Sweeps: drop the table entries whose ids no device store names any more (the flags come
+ * from dg_mark_ids over every live state).  No id moves, so nothing is remapped and every
+ * tree stays valid; a dropped id may be handed out again to another term, and a dropped term
+ * interned later gets a fresh id between its neighbours (the same choice as the Python
+ * Universe).  Node ids and canonical integer values are not swept.  ops.drop is called once
+ * per dropped term.
+ * Values: used[i] belongs to the i-th table value (dgm_value_hashes order); n must equal
+ * dgm_value_count (DG_E_INVAL otherwise, nothing dropped); vid/vterm/vhash compacted in place. */
+int dgm_sweep_values(dgm_universe* u, const uint8_t* used, uint64_t n, uint64_t* dropped);
+/* Keys: the key ids ascending (owned by the universe, valid until its next key insert, sweep
+ * or call of this) -- the table dg_mark_ids takes -- and the sweep by flags in that order
+ * (n must equal dgm_key_count and ids_sorted hold every key: DG_E_INVAL otherwise, nothing
+ * dropped). */
+uint64_t dgm_key_count(const dgm_universe* u);
+int dgm_key_ids_sorted(dgm_universe* u, const uint64_t** ids, uint64_t* n);
+int dgm_sweep_keys(dgm_universe* u, const uint64_t* ids_sorted, const uint8_t* used, uint64_t n,
+                   uint64_t* dropped);
+
 int dgm_node(dgm_universe* u, const void* term, uint32_t* id);
 const void* dgm_node_term(const dgm_universe* u, uint32_t id); /* NULL if unknown */
 uint32_t dgm_node_count(const dgm_universe* u);

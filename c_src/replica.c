@@ -61,6 +61,9 @@ struct dgr_engine {
   uint64_t ckeys_cap, h_ckeys_cap, h_cstage_cap;
   uint8_t* h_bin;
   uint64_t bin_cap;
+  /* dgr_sweep: the live states' stores as one host array */
+  dg_store* sw_stores;
+  uint64_t sw_cap;
 };
 
 #define TRY(x)                     \
@@ -302,6 +305,7 @@ int dgr_engine_close(dgr_engine* g) {
   dg_host_free(e, g->h_ckeys);
   dg_host_free(e, g->h_cstage);
   free(g->h_bin);
+  free(g->sw_stores);
   const int rc = dg_engine_destroy(e);
   free(g);
   return rc;
@@ -346,6 +350,36 @@ int dgr_remap(dgr_engine* g, const uint64_t* old_ids, const uint64_t* new_ids, u
   TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, 2 * n * 8));
   for (dgr_state* s = g->live; s; s = s->next)
     TRY(dg_remap_values(g->e, &s->rows, g->d_msg, g->d_msg + n, n));
+  return DG_OK;
+}
+
+int dgr_sweep(dgr_engine* g, int column, const uint64_t* ids, uint64_t n_ids, const uint8_t** used,
+              uint64_t* n_used, uint64_t* n_unknown) {
+  if (!g || !used || !n_used || (n_ids && !ids)) return DG_E_INVAL;
+  *used = NULL;
+  *n_used = 0;
+  if (g->n_live > g->sw_cap) {
+    const uint64_t want = umax(g->n_live, 2 * g->sw_cap) + 4;
+    dg_store* q = (dg_store*)realloc(g->sw_stores, want * sizeof *q);
+    if (!q) return DG_E_NOMEM;
+    g->sw_stores = q;
+    g->sw_cap = want;
+  }
+  uint64_t k = 0;
+  for (dgr_state* s = g->live; s; s = s->next) g->sw_stores[k++] = s->rows;
+  /* the table goes down in the message buffer; the flags come home in the return block
+   * (page-locked: the kernel writes them there, no copy and no second wait) */
+  TRY(grow_msg(g, n_ids + 1));
+  TRY(grow_back(g, (n_ids + 47) / 48, 0));
+  if (n_ids) {
+    memcpy(g->h_msg, ids, n_ids * 8);
+    TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, n_ids * 8));
+  }
+  TRY(dg_mark_ids(g->e, g->sw_stores, k, column, g->d_msg, n_ids, (uint8_t*)g->h_back, n_used, n_unknown));
+  /* the caller drops table entries by these flags: the device copies of the value table are
+   * re-uploaded before the next tree call (the key table has no device copy) */
+  if (column == DG_COL_VAL) g->th_stale = 1;
+  *used = (const uint8_t*)g->h_back;
   return DG_OK;
 }
 

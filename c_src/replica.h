@@ -61,6 +61,22 @@ int dgr_refresh_terms(dgr_engine* g, const uint64_t* node_hash, uint64_t n_nodes
  * the term tables stale.  Versions do not change: the terms the rows stand for do not. */
 int dgr_remap(dgr_engine* g, const uint64_t* old_ids, const uint64_t* new_ids, uint64_t n);
 
+/* Which ids of the universe's value table (column DG_COL_VAL: dgm_value_hashes' ids) or key
+ * table (DG_COL_KEY: dgm_key_ids_sorted) do the engine's live states still hold?  Uploads the
+ * table (host ids, strictly ascending: the device verifies it, DG_E_ORDER), marks over the
+ * rows of ALL live states with one dg_mark_ids call, and returns the flags as a host view
+ * into the engine's page-locked return block (valid until the next call on the engine),
+ * *n_used of them set.  *n_unknown (may be NULL): rows whose id the table lacks (canonical
+ * integers aside) -- non-zero on the value column means the table is not this engine's, and
+ * nothing must be dropped.  The caller then drops the unflagged entries (dgm_sweep_values /
+ * dgm_sweep_keys); after a value sweep the term tables are stale and the next
+ * dgr_refresh_terms uploads the smaller ones.  Versions do not change: the terms the rows
+ * stand for do not.  Deltas in flight are not resident: a value or key interned for a delta
+ * that has not been joined yet must be kept by the caller (the NIF sweeps under the engine
+ * mutex, between calls). */
+int dgr_sweep(dgr_engine* g, int column, const uint64_t* ids, uint64_t n_ids, const uint8_t** used,
+              uint64_t* n_used, uint64_t* n_unknown);
+
 /* A replica's state marshalled by a map walk (rows in any order, a context in any order:
  * a %{node => max} VV or a MapSet of dots) -> a device-resident state, version 1. */
 int dgr_state_load(dgr_engine* g, const dg_store* rows, const dg_context* ctx, dgr_state** out);

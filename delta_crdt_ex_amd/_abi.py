@@ -56,6 +56,9 @@ DG_HOME_WORDS = DG_HOME_CTX + DG_HOME_NODES + DG_HOME_NODES // 2
 DG_CTX_VV = 0
 DG_CTX_DOTS = 1
 
+DG_COL_KEY = 0
+DG_COL_VAL = 1
+
 P64 = C.POINTER(C.c_uint64)
 PI64 = C.POINTER(C.c_int64)
 P32 = C.POINTER(C.c_uint32)
@@ -231,6 +234,8 @@ _SIGS = {
     "dg_sort_store": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_store)]),
     "dg_sort_context": (C.c_int, [C.c_void_p, C.POINTER(dg_context), C.POINTER(dg_context)]),
     "dg_remap_values": (C.c_int, [C.c_void_p, C.POINTER(dg_store), P64, P64, C.c_uint64]),
+    "dg_mark_ids": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.c_uint64, C.c_int, P64, C.c_uint64,
+                              C.c_void_p, P64, P64]),
     "dg_merkle_chunks": (C.c_uint64, [C.c_uint32]),
     "dg_merkle_build": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_merkle)]),
     "dg_merkle_build_async": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_merkle),

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import interning
-from ._abi import DG_CTX_DOTS, DG_CTX_VV, FunctionClauseError
+from ._abi import DG_COL_KEY, DG_COL_VAL, DG_CTX_DOTS, DG_CTX_VV, FunctionClauseError
 from .store import Context, Engine, MerkleTree, Store, TermHashes, u64
 
 _ENGINE: Engine | None = None
@@ -306,5 +306,42 @@ def mutate_batch(ops, node_id, state: AWLWWMap):
     return AWLWWMap(delta, dots, U), [U.key_term(int(k)) for k in u64(keys)]
 
 
+def sweep(universe: interning.Universe | None = None, keys: bool = False, keep_values=(),
+          keep_keys=()) -> dict:
+    """Drop the universe's dead interning entries: the table values (and, with `keys`, the
+    keys) that no row of any device store still names.  The stores are `universe.tracked()`:
+    every live store that holds the universe's ids, states and deltas alike; which ids they
+    hold is asked of the device (dg_mark_ids: one pass over a column of every store, no
+    download), then `Universe.sweep` drops the rest.
+
+    Contract: an id handed out before the sweep (by `Universe.value` / `Universe.key`, or
+    read from a store since freed) that is in no swept store is DEAD afterwards and may be
+    issued again to another term.  A caller that holds bare ids, or terms it is about to put
+    into a delta, across a sweep pins them with `keep_values` / `keep_keys` (terms).  Node ids
+    and canonical integer values are never swept.  Nothing calls this automatically: a timer,
+    or `value_count()` against a multiple of the live rows, is the caller's policy.
+
+    Raises when a store holds a value id the table has lost (nothing is dropped then).
+    Returns {"values": (before, after), "keys": (before, after)}."""
+    U = universe or interning.DEFAULT
+    eng = engine()
+    stores = [st for st in U.tracked() if st.n]
+    vids, _terms = U.value_ids()
+    used_v, _n, unknown = eng.mark_ids(stores, DG_COL_VAL, np.array(vids, dtype=np.uint64))
+    if unknown:
+        raise RuntimeError(f"sweep: {unknown} rows hold a value id that is not in the universe's table")
+    used_k = None
+    if keys:
+        used_k, _n, unknown = eng.mark_ids(stores, DG_COL_KEY, U.key_ids())
+        if unknown:
+            raise RuntimeError(f"sweep: {unknown} rows hold a key id the universe does not know")
+        used_k = used_k.cpu().numpy()
+    out = U.sweep(used_v.cpu().numpy(), used_k, keep_values=keep_values, keep_keys=keep_keys)
+    for m in list(_LIVE):
+        if m.universe is U:
+            m._host = None
+    return out
+
+
 __all__ = ["AWLWWMap", "new", "compress_dots", "add", "remove", "clear", "join", "join_all", "read",
-           "mutate_batch", "from_terms", "merkle_map", "merkle_diff", "DG_CTX_VV", "DG_CTX_DOTS"]
+           "mutate_batch", "sweep", "from_terms", "merkle_map", "merkle_diff", "DG_CTX_VV", "DG_CTX_DOTS"]

@@ -2269,6 +2269,53 @@ int dg_remap_values(dg_engine* e, dg_store* s, const uint64_t* old_ids, const ui
   return DG_OK;
 }
 
+static_assert(DG_MARK_COL_KEY == DG_COL_KEY && DG_MARK_COL_VAL == DG_COL_VAL, "deltagpu.h's columns are the kernels'");
+
+int dg_mark_ids(dg_engine* e, const dg_store* stores, uint64_t n_stores, int column, const uint64_t* ids,
+                uint64_t n_ids, uint8_t* used, uint64_t* n_used, uint64_t* n_unknown) {
+  if (column != DG_COL_KEY && column != DG_COL_VAL) return fail(DG_E_INVAL, "dg_mark_ids: bad column %d", column);
+  if (n_stores && !stores) return fail(DG_E_INVAL, "dg_mark_ids: null stores with n_stores=%llu",
+                                       (unsigned long long)n_stores);
+  if (n_ids && (!ids || !used)) return fail(DG_E_INVAL, "dg_mark_ids: null id table or flags");
+  if (!n_used) return fail(DG_E_INVAL, "dg_mark_ids: null n_used");
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  if (n_ids >= (1ull << 40) || n_stores >= (1ull << 24))
+    return fail(DG_E_INVAL, "dg_mark_ids: more than 2^40 - 1 ids or 2^24 - 1 stores");
+  for (u64 i = 0; i < n_stores; i++) TRY(check_store(&stores[i], "dg_mark_ids"));
+  TRY(set_device(e));
+  TRY(settle(e));
+  // the stores' columns as one tile sequence: descriptors staged in pinned memory, copied on
+  // the engine stream ahead of the kernels (one launch chain whatever n_stores is)
+  const size_t seg_bytes = ((n_stores + 1) * sizeof(MarkSeg) + 255) / 256 * 256;
+  TRY(ensure_stage(e, std::max<size_t>(seg_bytes, 8 * 256 * sizeof(u32))));
+  const size_t bm_bytes = (mark_bitmap_words(n_ids) * sizeof(u32) + 255) / 256 * 256;
+  TRY(ensure_tmp(e, seg_bytes + bm_bytes + MARK_LDS_IDS * sizeof(u64)));
+  MarkSeg* hs = (MarkSeg*)e->h_stage;
+  u64 tiles = 0;
+  for (u64 i = 0; i < n_stores; i++) tiles += mark_tiles(stores[i].n, MARK_TILE_SMALL);
+  const u64 tile_rows = column == DG_COL_KEY && tiles <= MARK_SMALL_TILES ? MARK_TILE_SMALL : MARK_TILE;
+  tiles = 0;
+  for (u64 i = 0; i < n_stores; i++) {
+    hs[i].col = column == DG_COL_KEY ? stores[i].key : stores[i].val;
+    hs[i].n = stores[i].n;
+    hs[i].tile0 = tiles;
+    tiles += mark_tiles(stores[i].n, tile_rows);
+  }
+  hs[n_stores] = MarkSeg{nullptr, 0, tiles};
+  MarkSeg* ds = (MarkSeg*)e->tmp;
+  u32* bitmap = (u32*)((char*)e->tmp + seg_bytes);
+  u64* samples = (u64*)((char*)e->tmp + seg_bytes + bm_bytes);
+  if (tiles)
+    HIP_TRY(hipMemcpyAsync(ds, hs, (n_stores + 1) * sizeof(MarkSeg), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(launch_mark_ids(ds, n_stores + 1, tiles, tile_rows, column, mark_mode(column, n_ids), ids, n_ids, bitmap, samples, used,
+                          e->d_counts, e->ticket + 3, e->stream));
+  TRY(read_counts(e, 2));
+  if (e->h_ticket[3]) return fail(DG_E_ORDER, "dg_mark_ids: the id table is not strictly ascending");
+  *n_used = e->h_counts[0];
+  if (n_unknown) *n_unknown = e->h_counts[1];
+  return DG_OK;
+}
+
 int dg_sort_store(dg_engine* e, const dg_store* in, dg_store* out) {
   if (!e) return fail(DG_E_INVAL, "null engine");
   TRY(check_store(in, "dg_sort_store"));

@@ -277,6 +277,31 @@ hipError_t launch_sort_context(int kind, const u32* node, const u64* cnt, u64 n,
 hipError_t launch_remap_values(u64* val, u64 n, const u64* old_ids, const u64* new_ids, u64 n_ids,
                                u32* err, hipStream_t st);
 
+// ---- mark.hip (which ids of a host table the stores still hold; see the file header)
+constexpr int DG_MARK_COL_KEY = 0, DG_MARK_COL_VAL = 1;  // (deltagpu.h enum dg_column)
+constexpr int MARK_LDS_IDS = 2048;   // table entries (or samples, or window entries) staged in LDS
+constexpr u64 MARK_TILE = 2048;      // rows per tile; a tile never spans two stores
+constexpr u64 MARK_TILE_SMALL = 512;   // ... on the key column while the stores make at most
+constexpr u64 MARK_SMALL_TILES = 4096; //   MARK_SMALL_TILES of these (more workgroups: mark.hip)
+constexpr u64 MARK_MAX_GRID = 2048;  // workgroups of the pass (8 per CU: 16 KB of LDS each)
+enum { MARK_STAGED = 0, MARK_SAMPLED = 1, MARK_WINDOW = 2 };
+struct MarkSeg {  // one store's column; the table ends with a sentinel {nullptr, 0, n_tiles}
+  const u64* col;
+  u64 n;
+  u64 tile0;      // its first tile among all stores' tiles
+};
+inline u64 mark_tiles(u64 n, u64 tile_rows) { return (n + tile_rows - 1) / tile_rows; }
+// u32 words: the bits, plus the tail an LDS bitmap's flush may read past them (mark.hip)
+inline u64 mark_bitmap_words(u64 n_ids) { return (n_ids + 31) / 32 + MARK_LDS_IDS / 32 + 2; }
+int mark_mode(int column, u64 n_ids);
+// bitmap: mark_bitmap_words(n_ids) u32 of scratch; samples: MARK_LDS_IDS u64 of scratch; used: n_ids bytes (device or mapped host
+// memory); d_counts[0] = ids used, d_counts[1] = rows whose id is not in the table (canonical
+// integer values not counted on the value column); *bad = 1 when ids is not strictly ascending.
+// All three are zeroed by the chain itself.
+hipError_t launch_mark_ids(const MarkSeg* segs, u64 n_segs, u64 n_tiles, u64 tile_rows, int column, int mode,
+                           const u64* ids, u64 n_ids, u32* bitmap, u64* samples, uint8_t* used, u64* d_counts,
+                           u32* bad, hipStream_t st);
+
 // ---- merkle.hip (see the file header)
 // term hashes of a tree's rows (dg_term_hashes; on = 0: the ids themselves)
 struct TermH {

@@ -283,6 +283,63 @@ class Universe:
         ascending (= term order)."""
         return list(self._val_ids), [self._val_term[v] for v in self._val_ids]
 
+    def value_count(self) -> int:
+        """The number of table values (the canonical integers have no entry)."""
+        return len(self._val_ids)
+
+    def key_count(self) -> int:
+        return len(self._key_term)
+
+    def key_ids(self) -> np.ndarray:
+        """The interned key ids, ascending (the table a key sweep marks against)."""
+        return np.array(sorted(self._key_term), dtype=np.uint64)
+
+    def sweep(self, used_values, used_keys=None, keep_values=(), keep_keys=()):
+        """Drop the table values and keys no store names any more.  `used_values`: one flag
+        per id of `value_ids()`, in that order (dg_mark_ids over every store that holds this
+        Universe's ids); `used_keys` (None: keys are not swept): one flag per id of
+        `key_ids()`.  `keep_values` / `keep_keys`: TERMS that stay whatever their flag says
+        (ids a caller still holds outside any store).  A dropped id is dead: `value_term` /
+        `key_term` of it raises KeyError, and it may be issued again to another term; a later
+        `value(t)` of a dropped term interns it afresh between its neighbours.  No id moves,
+        so `val_epoch` stays, no store is remapped and every tree stays valid; `terms_version`
+        moves, so the device copies of the (smaller) term-hash tables are refreshed.  Node ids
+        (dense, named by every context) and canonical integers (no table) are not swept.
+        Returns {"values": (before, after), "keys": (before, after)}."""
+        used_values = np.asarray(used_values).astype(bool).ravel()
+        nv = len(self._val_ids)
+        if len(used_values) != nv:
+            raise ValueError(f"sweep: {len(used_values)} value flags for {nv} table values")
+        pinned = {_hkey(t) for t in keep_values}
+        keep = [bool(used_values[i]) or self._val_keys[i] in pinned for i in range(nv)]
+        nk = len(self._key_term)
+        kids = None
+        if used_keys is not None:
+            used_keys = np.asarray(used_keys).astype(bool).ravel()
+            kids = sorted(self._key_term)
+            if len(used_keys) != nk:
+                raise ValueError(f"sweep: {len(used_keys)} key flags for {nk} keys")
+        if not all(keep):
+            for i in range(nv):
+                if not keep[i]:
+                    del self._val_term[self._val_ids[i]]
+                    del self._val_id[self._val_keys[i]]
+            self._val_keys = [x for x, k in zip(self._val_keys, keep) if k]
+            self._val_ids = [x for x, k in zip(self._val_ids, keep) if k]
+            self._val_hash = [x for x, k in zip(self._val_hash, keep) if k]
+        if kids is not None:
+            pinned_k = {_hkey(t) for t in keep_keys}
+            for kid, u in zip(kids, used_keys):
+                if u:
+                    continue
+                hk = _hkey(self._key_term[kid])
+                if hk in pinned_k:
+                    continue
+                del self._key_term[kid]
+                del self._key_id[hk]
+        self.terms_version += 1
+        return {"values": (nv, len(self._val_ids)), "keys": (nk, len(self._key_term))}
+
     def track(self, store):
         """Remember a device store whose `val` column holds this Universe's ids (the
         remap hook rewrites it on a relabel)."""

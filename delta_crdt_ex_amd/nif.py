@@ -16,6 +16,8 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
     merkle_prepare(state, version, levels)          -> ("continue", bytes)
     merkle_continue(state, version, cont, levels, max_sync_size | "infinite")
                                                     -> ("continue", bytes) | ("ok", keys)
+    sweep(engine)                                   -> ("ok", {"values": (before, after),
+                                                               "keys": (before, after)})
     resolve_keys(engine, keys)                      -> keys
     errors: ("error", "stale") for a version that is not the state's (an older struct),
             ("error", (code, message)) otherwise.
@@ -62,6 +64,7 @@ _SIGS = {
     "dgr_dg": (VP, [VP]),
     "dgr_refresh_terms": (I32, [VP, VP, U64, VP, VP, U64]),
     "dgr_remap": (I32, [VP, VP, VP, U64]),
+    "dgr_sweep": (I32, [VP, I32, VP, U64, C.POINTER(VP), PU64, PU64]),
     "dgr_state_load": (I32, [VP, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP)]),
     "dgr_state_free": (I32, [VP]),
     "dgr_state_version": (U64, [VP]),
@@ -136,6 +139,41 @@ class Engine:
         nh, vid, vh = self.universe.term_tables()
         return self.lib.dgr_refresh_terms(self.ptr, nh.ctypes.data, len(nh), vid.ctypes.data,
                                           vh.ctypes.data, len(vid))
+
+    def _mark(self, column: int, ids: np.ndarray):
+        """dgr_sweep: the flags of `ids` (ascending) over the rows of every live state"""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        p, nu, nx = VP(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.dgr_sweep(self.ptr, column, ids.ctypes.data, len(ids), C.byref(p), C.byref(nu),
+                                C.byref(nx))
+        if rc:
+            return rc, None, 0
+        used = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(len(ids),)).copy()
+                if len(ids) else np.zeros(0, np.uint8))
+        return 0, used, int(nx.value)
+
+    def sweep(self, keys: bool = True, keep_values=(), keep_keys=()):
+        """Drop the universe's table values (and keys) that no live state of this engine
+        names any more (dgr_sweep + Universe.sweep; the NIF's sweep/1 does the same with
+        dgm_sweep_values / dgm_sweep_keys).  State versions do not change.  Terms on their
+        way into a delta that is not joined yet are pinned with keep_values / keep_keys.
+        Returns the NIF's shape: ("ok", {"values": (before, after), "keys": (before, after)})."""
+        U = self.universe
+        vids, _t = U.value_ids()
+        rc, used_v, unknown = self._mark(_abi.DG_COL_VAL, np.array(vids, np.uint64))
+        if rc:
+            return _err(rc)
+        if unknown:
+            return ("error", (_abi.DG_E_INVAL, f"{unknown} rows hold a value id the table lacks"))
+        used_k = None
+        if keys:
+            rc, used_k, unknown = self._mark(_abi.DG_COL_KEY, U.key_ids())
+            if rc:
+                return _err(rc)
+            if unknown:
+                return ("error", (_abi.DG_E_INVAL, f"{unknown} rows hold a key id the table lacks"))
+        return ("ok", U.sweep(used_v, used_k, keep_values=[self.unwrap(t) for t in keep_values],
+                              keep_keys=[self.unwrap(t) for t in keep_keys]))
 
     def close(self):
         for s in self.states:
@@ -414,6 +452,10 @@ def merkle_continue(state: State, version: int, cont: bytes, levels: int, max_sy
     return ("ok", [_key_term(eng, kid) for kid in _arr(pk, nk.value, np.uint64)])
 
 
+def sweep(engine: Engine, keys: bool = True):
+    return engine.sweep(keys=keys)
+
+
 def _key_term(eng: Engine, kid):
     """the key's term, or its placeholder when this node never interned it"""
     try:
@@ -437,5 +479,5 @@ def resolve_keys(engine: Engine, keys):
 
 
 __all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "read", "take",
-           "merkle_build", "merkle_prepare", "merkle_continue", "resolve_keys", "key_placeholder",
+           "merkle_build", "merkle_prepare", "merkle_continue", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

@@ -943,6 +943,26 @@ class Engine:
         check(self.lib.dg_remap_values(self.h, C.byref(ss), _ptr(o, _abi.P64), _ptr(w, _abi.P64),
                                        int(len(old_ids))))
 
+    def mark_ids(self, stores, column: int, ids):
+        """dg_mark_ids: which of `ids` (strictly ascending u64 ids: a numpy array, or a device
+        int64 tensor holding their bits) occur in `column` (_abi.DG_COL_KEY / DG_COL_VAL) of
+        some row of `stores`.  Returns (used, n_used, n_unknown): a device uint8 tensor of
+        len(ids) flags, the number of ones, and the number of rows whose id is not in `ids`
+        (canonical integer values not counted on the value column)."""
+        self._order()
+        if not isinstance(ids, torch.Tensor):
+            a = np.ascontiguousarray(np.asarray(ids, np.uint64))
+            ids = (_np_to_dev(a, np.int64, self.device) if len(a)
+                   else torch.zeros(0, dtype=_I64, device=self.device))
+        n = int(ids.numel())
+        used = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        k = len(stores)
+        arr = (_abi.dg_store * max(k, 1))(*[s.abi() for s in stores])
+        nu, nx = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.dg_mark_ids(self.h, arr, k, int(column), _ptr(ids, _abi.P64), n,
+                                   C.c_void_p(used.data_ptr()), C.byref(nu), C.byref(nx)))
+        return used[:n], int(nu.value), int(nx.value)
+
     def store_check(self, s: Store):
         self._order()
         ss = s.abi()

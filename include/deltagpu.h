@@ -464,6 +464,32 @@ int dg_sort_context(dg_engine* e, const dg_context* in, dg_context* out);
 int dg_remap_values(dg_engine* e, dg_store* s, const uint64_t* old_ids, const uint64_t* new_ids,
                     uint64_t n_ids);
 
+/* The host's key and value tables (interning.py Universe, c_src/marshal.c dgm_universe) keep
+ * the term of every id they ever handed out; only the device knows which ids its rows still
+ * name.  dg_mark_ids answers that for a table of ids, so the host can drop the dead entries
+ * (Universe.sweep, dgm_sweep_values / dgm_sweep_keys).  Node ids (dense, named by every
+ * context) and canonical integer values (no table entry) are not swept. */
+enum dg_column { DG_COL_KEY = 0, DG_COL_VAL = 1 };
+
+/* Which ids of a table are still referenced: used[j] = 1 iff some row of some
+ * stores[i] (i < n_stores) has ids[j] in `column`, else 0 (the call zeroes `used`).
+ *   stores     a HOST array of device stores (empty stores allowed; n_stores 0: nothing is used)
+ *   ids        device, STRICTLY ASCENDING, n_ids entries: verified on the device by the call
+ *              itself (DG_E_ORDER otherwise; `used` is then unspecified) -- a wrong table here
+ *              means live terms get deleted
+ *   used       n_ids bytes, device memory or memory from dg_host_alloc
+ *   *n_used    the number of ones
+ *   *n_unknown (may be NULL) the number of ROWS whose id is not in `ids`; on DG_COL_VAL rows
+ *              holding a canonical integer id ([2^58, 2^63), no table entry by design) are not
+ *              counted.  Non-zero on the value column: the host table has lost an id that a
+ *              store still holds.
+ * One streaming pass over the column of every store in one launch chain, ONE host wait
+ * whatever n_stores is.  The key column relies on the stores' own order (key ascending): a
+ * key out of order is counted unknown, not marked.  Synchronous. */
+int dg_mark_ids(dg_engine* e, const dg_store* stores, uint64_t n_stores, int column,
+                const uint64_t* ids, uint64_t n_ids, uint8_t* used,
+                uint64_t* n_used, uint64_t* n_unknown);
+
 /* ---- Merkle anti-entropy (MerkleMap role) --------------------------------- */
 /* Build the tree of `s` (MerkleMap.new + put of every key, causal_crdt.ex:21,390-394):
  * t->depth, shard_bits, shard, nodes, counts and terms set by the caller; sets t->n_keys.
