@@ -275,7 +275,7 @@ typedef struct {
 static ErlNifResourceType* ENGINE_RT;
 static ErlNifResourceType* STATE_RT;
 static ERL_NIF_TERM A_OK, A_ERROR, A_NIL, A_ALL, A_CONTINUE, A_MAP, A_STRUCT, A_MAPSET, A_STALE,
-    A_INFINITE, A_DGKEY;
+    A_INFINITE, A_DGKEY, A_ADD, A_REMOVE;
 
 static void engine_dtor(ErlNifEnv* env, void* obj) {
   (void)env;
@@ -647,9 +647,45 @@ static ERL_NIF_TERM state_load(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   return r;
 }
 
+/* diffs_to_callback/3's list (causal_crdt.ex:361-381) from the device's reads of the changed
+ * keys before and after the join: [{:add, key, value} | {:remove, key}] in ascending key-id
+ * order, the order of `changed` (the reference emits them in `keys` order; a consumer must
+ * not rely on the order inside one callback list) */
+static int diffs_list(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const dgr_diffs* d,
+                      ERL_NIF_TERM* out) {
+  ERL_NIF_TERM l = enif_make_list(env, 0);
+  boxed bn = {A_NIL};
+  uint64_t nil_id = 0;
+  const int has_nil = dgm_value_find(g->u, &bn, &nil_id);
+  if (has_nil < 0) return has_nil;
+  uint8_t* kind = (uint8_t*)enif_alloc(d->n ? d->n : 1);
+  if (!kind) return DG_E_NOMEM;
+  dgm_classify_diffs(d->old_val, d->new_val, d->flags, d->n, has_nil, nil_id, kind);
+  int rc = DG_OK;
+  for (uint64_t i = d->n; i-- > 0 && !rc;) {
+    if (kind[i] == DGM_DIFF_NONE) continue;
+    const boxed* b = (const boxed*)dgm_key_term(g->u, c->keys[i]);
+    if (!b) {
+      rc = DG_E_INVAL;
+      break;
+    }
+    ERL_NIF_TERM k = enif_make_copy(env, b->t), v;
+    if (kind[i] == DGM_DIFF_REMOVE) {
+      l = enif_make_list_cell(env, enif_make_tuple2(env, A_REMOVE, k), l);
+    } else if (!(rc = value_term(env, g, d->new_val[i], &v))) {
+      l = enif_make_list_cell(env, enif_make_tuple3(env, A_ADD, k, v), l);
+    }
+  }
+  enif_free(kind);
+  *out = l;
+  return rc;
+}
+
 /* {:ok, version, new_dots, [{key, value_map | nil}]} from a join's result: the changed
- * keys' rows (in key order) walked into value maps, the context into its term */
-static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, ERL_NIF_TERM* r) {
+ * keys' rows (in key order) walked into value maps, the context into its term; with `d`
+ * {:ok, version, new_dots, changed, diffs} */
+static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const dgr_diffs* d,
+                          ERL_NIF_TERM* r) {
   ERL_NIF_TERM values, dots, changed = enif_make_list(env, 0);
   int rc = unmarshal_host_rows(env, g, &c->rows, &values);
   if (!rc) rc = unmarshal_dots(env, g, &c->ctx, &dots);
@@ -661,6 +697,12 @@ static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, E
     if (!enif_get_map_value(env, values, k, &v)) v = A_NIL; /* the key's entries all went */
     changed = enif_make_list_cell(env, enif_make_tuple2(env, k, v), changed);
   }
+  if (d) {
+    ERL_NIF_TERM diffs;
+    if ((rc = diffs_list(env, g, c, d, &diffs))) return rc;
+    *r = enif_make_tuple5(env, A_OK, enif_make_uint64(env, c->version), dots, changed, diffs);
+    return DG_OK;
+  }
   *r = enif_make_tuple4(env, A_OK, enif_make_uint64(env, c->version), dots, changed);
   return DG_OK;
 }
@@ -669,8 +711,7 @@ static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, E
  * join/3 (aw_lww_map.ex:153-158) of the resident state with the delta %{dots, value} over
  * `keys`, in place on the device; `changed` = the keys whose raw value maps changed
  * (causal_crdt.ex:344-352) with their new maps; the tree (if built) gets their put/delete. */
-static ERL_NIF_TERM join_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  (void)argc;
+static ERL_NIF_TERM join_delta_impl(ErlNifEnv* env, const ERL_NIF_TERM argv[], int with_diffs) {
   state_res* s;
   uint64_t version;
   if (!get_state(env, argv[0], argv[1], &s, &version)) return enif_make_badarg(env);
@@ -686,8 +727,14 @@ static ERL_NIF_TERM join_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   TRY(marshal_value(env, g, argv[3], &h));
   TRY(marshal_keys(env, g, argv[4], &keys, &n_keys));
   if (dgr_state_has_tree(s->s)) TRY(refresh_terms(g));
-  TRY(dgr_join_delta(s->s, version, &h.s, &h.c, keys, n_keys, &c));
-  TRY(changed_result(env, g, &c, &r));
+  if (with_diffs) {
+    dgr_diffs d;
+    TRY(dgr_join_delta_diffs(s->s, version, &h.s, &h.c, keys, n_keys, &c, &d));
+    TRY(changed_result(env, g, &c, &d, &r));
+  } else {
+    TRY(dgr_join_delta(s->s, version, &h.s, &h.c, keys, n_keys, &c));
+    TRY(changed_result(env, g, &c, NULL, &r));
+  }
 out:
   if (rc) r = error_term(env, rc);
   dgm_rows_free(&h);
@@ -696,14 +743,26 @@ out:
   return r;
 }
 
+static ERL_NIF_TERM join_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return join_delta_impl(env, argv, 0);
+}
+
+/* join_delta_diffs(state, version, dots, value, keys) -> {:ok, version', new_dots, changed,
+ * diffs}: join_delta plus what on_diffs receives, from the device's reads of the changed keys
+ * before and after the join (dgr_join_delta_diffs) -- no old struct is read */
+static ERL_NIF_TERM join_delta_diffs(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return join_delta_impl(env, argv, 1);
+}
+
 /* mutate_batch(state, version, node, ops) -> {:ok, version', new_dots, changed}: a batch of
  * mutations by `node` -- ops = [{:add, key, value, ts} | {:remove, key}] in the order they
  * were made (the queued mutations of a GPU-attached replica, causal_crdt.ex:196-198,
  * 337-342) -- as ONE delta built on the device (dg_mutate_batch: per touched key the last
  * op's row if it is an add, context = the touched keys' dots plus every add's dot,
  * aw_lww_map.ex:99-146), applied like join_delta with the touched keys. */
-static ERL_NIF_TERM mutate_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  (void)argc;
+static ERL_NIF_TERM mutate_batch_impl(ErlNifEnv* env, const ERL_NIF_TERM argv[], int with_diffs) {
   state_res* s;
   uint64_t version;
   unsigned m;
@@ -766,8 +825,14 @@ static ERL_NIF_TERM mutate_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TER
     }
   }
   if (dgr_state_has_tree(s->s)) TRY(refresh_terms(g));
-  TRY(dgr_mutate_batch(s->s, version, node, m, kind, key, val, ts, &c));
-  TRY(changed_result(env, g, &c, &r));
+  if (with_diffs) {
+    dgr_diffs d;
+    TRY(dgr_mutate_batch_diffs(s->s, version, node, m, kind, key, val, ts, &c, &d));
+    TRY(changed_result(env, g, &c, &d, &r));
+  } else {
+    TRY(dgr_mutate_batch(s->s, version, node, m, kind, key, val, ts, &c));
+    TRY(changed_result(env, g, &c, NULL, &r));
+  }
 out:
   if (rc) r = error_term(env, rc);
   if (kind) enif_free(kind);
@@ -776,6 +841,18 @@ out:
   if (ts) enif_free(ts);
   enif_mutex_unlock(g->lock);
   return r;
+}
+
+static ERL_NIF_TERM mutate_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return mutate_batch_impl(env, argv, 0);
+}
+
+/* mutate_batch_diffs(state, version, node, ops) -> {:ok, version', new_dots, changed, diffs}:
+ * mutate_batch plus on_diffs' list for the batch's net changes (dgr_mutate_batch_diffs) */
+static ERL_NIF_TERM mutate_batch_diffs_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return mutate_batch_impl(env, argv, 1);
 }
 
 /* read(state, version, keys | :all) -> {:ok, %{key => value}}  (read/1,2, :211-224) */
@@ -985,6 +1062,8 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   A_STALE = enif_make_atom(env, "stale");
   A_INFINITE = enif_make_atom(env, "infinite");
   A_DGKEY = enif_make_atom(env, "$dg_key");
+  A_ADD = enif_make_atom(env, "add");
+  A_REMOVE = enif_make_atom(env, "remove");
   return (ENGINE_RT && STATE_RT) ? 0 : 1;  /* a failed load -> the Elixir code path */
 }
 
@@ -993,6 +1072,8 @@ static ErlNifFunc funcs[] = {
     {"state_load", 3, state_load, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"join_delta", 5, join_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"mutate_batch", 4, mutate_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"join_delta_diffs", 5, join_delta_diffs, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"mutate_batch_diffs", 4, mutate_batch_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"read", 3, read_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"take", 3, take_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_build", 3, merkle_build_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},

@@ -417,6 +417,33 @@ int dgm_value(dgm_universe* u, const void* term, uint64_t* id, int* relabeled) {
   return DG_OK;
 }
 
+int dgm_value_find(dgm_universe* u, const void* term, uint64_t* id) {
+  const int rc = encode(u, term);
+  if (rc) return rc;
+  int64_t cv;
+  if (enc_canonical(u->enc.p, u->enc.n, &cv)) {
+    *id = (uint64_t)cv + (1ull << 62);
+    return 1;
+  }
+  int eq;
+  const uint64_t p = value_lb(u, term, &eq);
+  if (eq) *id = u->vid[p];
+  return eq;
+}
+
+void dgm_classify_diffs(const uint64_t* old_val, const uint64_t* new_val, const uint8_t* flags, uint64_t n,
+                        int has_nil, uint64_t nil_id, uint8_t* kind) {
+  for (uint64_t i = 0; i < n; i++) {
+    /* Map.get(read, key) (causal_crdt.ex:369): nil for an absent key and for a nil value */
+    const int o = (flags[i] & DG_DIFF_OLD) && !(has_nil && old_val[i] == nil_id);
+    const int w = (flags[i] & DG_DIFF_NEW) && !(has_nil && new_val[i] == nil_id);
+    if (!w)
+      kind[i] = o ? DGM_DIFF_REMOVE : DGM_DIFF_NONE; /* {nil, nil} is {old, old}; {_old, nil} */
+    else
+      kind[i] = (o && old_val[i] == new_val[i]) ? DGM_DIFF_NONE : DGM_DIFF_ADD;
+  }
+}
+
 const void* dgm_value_term(const dgm_universe* u, uint64_t id) {
   uint64_t lo = 0, hi = u->nv;
   while (lo < hi) {

@@ -98,6 +98,9 @@ const void* dgm_key_term(const dgm_universe* u, uint64_t id); /* NULL if unknown
 /* *relabeled = 1 when this insert re-spaced the value ids of its region: dgm_last_relabel
  * then hands out the (old, new) id arrays, both ascending, for dg_remap_values. */
 int dgm_value(dgm_universe* u, const void* term, uint64_t* id, int* relabeled);
+/* The id `term` has as a value WITHOUT interning it: 1 and *id when it is a canonical integer
+ * or in the table, 0 when it was never interned (no row can hold it), < 0 an encode error. */
+int dgm_value_find(dgm_universe* u, const void* term, uint64_t* id);
 /* The term of a table value id; NULL if unknown and for canonical integer ids (the caller
  * makes those from dgm_value_is_canonical). */
 const void* dgm_value_term(const dgm_universe* u, uint64_t id);
@@ -133,6 +136,19 @@ uint32_t dgm_node_count(const dgm_universe* u);
 void dgm_node_hashes(const dgm_universe* u, const uint64_t** hash, uint32_t* n);
 void dgm_value_hashes(const dgm_universe* u, const uint64_t** ids, const uint64_t** hash,
                       uint64_t* n);
+
+/* diffs_to_callback/3's case (causal_crdt.ex:368-374) over value ids, per changed key: the
+ * device's reads before and after a join (dg_lww_diffs: old_val, new_val, flags) ->
+ * kind[i] = DGM_DIFF_NONE (`{old, old} -> []`), DGM_DIFF_ADD (`{:add, key, new}`) or
+ * DGM_DIFF_REMOVE (`{_old, nil} -> {:remove, key}`).  A side is absent when its flag is
+ * clear or its id is nil's: Map.get gives nil either way.  has_nil / nil_id:
+ * dgm_value_find of the nil term (has_nil 0: nil was never interned, so no row holds it).
+ * Id equality is the reference's `{old, old}` match: 1 and 1.0 have different ids. */
+#define DGM_DIFF_NONE 0
+#define DGM_DIFF_ADD 1
+#define DGM_DIFF_REMOVE 2
+void dgm_classify_diffs(const uint64_t* old_val, const uint64_t* new_val, const uint8_t* flags, uint64_t n,
+                        int has_nil, uint64_t nil_id, uint8_t* kind);
 
 /* host rows and a context, grown on demand (the columns of a dg_store / dg_context) */
 typedef struct dgm_rows {

@@ -43,10 +43,13 @@ struct dgr_engine {
   uint64_t* mkeys;
   uint64_t mkeys_cap;
   /* the return block (words): changed keys [0, S) | key | val | ts | cnt [S, 5S) |
-   * node u32 [5S, 6S) | context cnt [6S, 6S + C) | context node u32 [6S + C, 6S + 2C) */
+   * node u32 [5S, 6S) | context cnt [6S, 6S + C) | context node u32 [6S + C, 6S + 2C) |
+   * the changed keys' old value ids [D, D + S) | new [D + S, D + 2S) | flags u8 [D + 2S,
+   * D + 2S + S / 8], D = 6S + 2C (the *_diffs calls) */
   uint64_t *d_back, *h_back;
   uint64_t back_s, back_c;
-  /* dg_join_delta_home's result block (page-locked, DG_HOME_WORDS) */
+  /* dg_join_delta_home's result block (page-locked, DG_HOME_DIFFS_WORDS: the plain call
+   * writes a prefix of it) */
   uint64_t* h_home;
   /* read output: keys [0, cap) | values [cap, 2 cap) */
   uint64_t *d_rd, *h_rd;
@@ -161,11 +164,19 @@ static int grow_back(dgr_engine* g, uint64_t S, uint64_t C) {
   TRY(dg_host_free(g->e, g->h_back));
   g->d_back = g->h_back = NULL;
   g->back_s = g->back_c = 0;
-  TRY(dg_buffer_alloc(g->e, (6 * S + 2 * C) * 8, (void**)&g->d_back));
-  TRY(dg_host_alloc(g->e, (6 * S + 2 * C) * 8, (void**)&g->h_back));
+  const uint64_t words = 6 * S + 2 * C + 2 * S + S / 8 + 1;
+  TRY(dg_buffer_alloc(g->e, words * 8, (void**)&g->d_back));
+  TRY(dg_host_alloc(g->e, words * 8, (void**)&g->h_back));
   g->back_s = S;
   g->back_c = C;
   return DG_OK;
+}
+
+/* the block's diff arrays (S entries each) */
+static dg_lww_diffs back_diffs(uint64_t* b, uint64_t S, uint64_t C) {
+  uint64_t* d = b + 6 * S + 2 * C;
+  dg_lww_diffs r = {d, d + S, (uint8_t*)(d + 2 * S), S};
+  return r;
 }
 
 static dg_store back_rows(uint64_t* b, uint64_t S) {
@@ -488,14 +499,16 @@ static int small_fits(const dgr_state* s, const dg_store* drows, const dg_contex
 }
 
 static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dctx, const uint64_t* dkeys,
-                       uint64_t n_keys, dgr_changed* out, int* done) {
+                       uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs, int* done) {
   dgr_engine* g = s->g;
   *done = 0;
   if (!small_fits(s, drows, dctx, n_keys)) return DG_OK;
-  if (!g->h_home) TRY(dg_host_alloc(g->e, DG_HOME_WORDS * 8, (void**)&g->h_home));
+  if (!g->h_home) TRY(dg_host_alloc(g->e, DG_HOME_DIFFS_WORDS * 8, (void**)&g->h_home));
   int swapped = 0;
-  const int rc = dg_join_delta_home(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
-                                    s->has_tree ? &s->tree : NULL, g->h_home, &swapped);
+  /* (diffs: the LWW reads before and after come out of the same kernel, the same wait) */
+  const int rc = (diffs ? dg_join_delta_home_diffs : dg_join_delta_home)(
+      g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare, s->has_tree ? &s->tree : NULL, g->h_home,
+      &swapped);
   if (rc) {
     s->version++;
     return rc;
@@ -514,18 +527,24 @@ static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dc
   dg_context c = {DG_CTX_VV, 0, (uint32_t*)(g->h_home + DG_HOME_CTX + DG_HOME_NODES),
                   g->h_home + DG_HOME_CTX, h[3], DG_HOME_NODES};
   out->ctx = c;
+  if (diffs) {
+    diffs->n = h[1];
+    diffs->old_val = h + DG_HOME_DIFF_OLD;
+    diffs->new_val = h + DG_HOME_DIFF_NEW;
+    diffs->flags = (const uint8_t*)(h + DG_HOME_DIFF_FLAGS);
+  }
   return DG_OK;
 }
 
 /* The join of a delta on the device (rows and context sorted, keys ascending unique) into
  * the state, and the result brought home with one wait.  try_small: the small join first. */
 static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dctx, const uint64_t* dkeys,
-                       uint64_t n_keys, dgr_changed* out, int try_small) {
+                       uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs, int try_small) {
   dgr_engine* g = s->g;
   TRY(room_for(s, drows->n, dctx->n));
   if (try_small) {
     int done = 0;
-    TRY(apply_small(s, drows, dctx, dkeys, n_keys, out, &done));
+    TRY(apply_small(s, drows, dctx, dkeys, n_keys, out, diffs, &done));
     if (done) return DG_OK;
   }
   /* the changed keys, their rows and the joined context straight into the page-locked
@@ -540,20 +559,43 @@ static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dc
   dg_context co = {DG_CTX_VV, 0, (uint32_t*)(hb + 6 * S + C), hb + 6 * S, 0, C};
   uint64_t n_changed = 0;
   int swapped = 0;
-  const int rc = dg_join_delta_out(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
-                                   s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk, &co);
+  dg_lww_diffs dd = back_diffs(hb, S, C);
+  const int rc = diffs ? dg_join_delta_diffs(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
+                                             s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk,
+                                             &co, &dd)
+                       : dg_join_delta_out(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
+                                           s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk, &co);
   s->version++; /* applied, or failed: either way no older struct reads the device again */
   TRY(rc);
+  if (diffs && dd.cap == 0 && n_changed) {
+    /* the gather behind the committed join failed (deltagpu.h): the old rows survive only
+     * where the join went through the spare store, which still describes them */
+    if (!swapped) return DG_E_DEVICE;
+    dd = back_diffs(hb, S, C);
+    TRY(dg_read_diff(g->e, &s->spare, &s->rows, hb, n_changed, &dd));
+  }
   if (tk.n > tk.cap || co.n > co.cap) {
-    /* park the changed keys, grow the block, take the rows from the joined state and copy
-     * the context (the kernels write the page-locked block directly) */
-    TRY(grow_msg(g, n_changed + 1));
+    /* park the changed keys (and their diffs), grow the block, take the rows from the
+     * joined state and copy the context (the kernels write the page-locked block directly) */
+    const uint64_t nf = (n_changed + 7) / 8; /* the flags' words */
+    TRY(grow_msg(g, diffs ? 3 * n_changed + nf + 1 : n_changed + 1));
     memcpy(g->h_msg, hb, n_changed * 8);
+    if (diffs) {
+      memcpy(g->h_msg + n_changed, dd.old_val, n_changed * 8);
+      memcpy(g->h_msg + 2 * n_changed, dd.new_val, n_changed * 8);
+      memcpy(g->h_msg + 3 * n_changed, dd.flags, n_changed);
+    }
     TRY(grow_back(g, umax(tk.n, n_changed), s->ctx.n));
     S = g->back_s;
     C = g->back_c;
     hb = g->h_back;
     memcpy(hb, g->h_msg, n_changed * 8);
+    if (diffs) {
+      dd = back_diffs(hb, S, C);
+      memcpy(dd.old_val, g->h_msg + n_changed, n_changed * 8);
+      memcpy(dd.new_val, g->h_msg + 2 * n_changed, n_changed * 8);
+      memcpy(dd.flags, g->h_msg + 3 * n_changed, n_changed);
+    }
     TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, n_changed * 8));
     tk = back_rows(hb, S);
     TRY(dg_take_keys(g->e, &s->rows, g->d_msg, n_changed, &tk));
@@ -570,11 +612,18 @@ static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dc
   out->rows.n = tk.n;
   dg_context c = {co.kind, 0, (uint32_t*)(hb + 6 * S + C), hb + 6 * S, co.n, C};
   out->ctx = c;
+  if (diffs) {
+    diffs->n = n_changed;
+    diffs->old_val = dd.old_val;
+    diffs->new_val = dd.new_val;
+    diffs->flags = dd.flags;
+  }
   return DG_OK;
 }
 
-int dgr_join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const dg_context* delta_ctx,
-                   const uint64_t* keys, uint64_t n_keys, dgr_changed* out) {
+/* dgr_join_delta (diffs NULL) and dgr_join_delta_diffs */
+static int join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const dg_context* delta_ctx,
+                      const uint64_t* keys, uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs) {
   if (!s || !delta || !delta_ctx || !out || (n_keys && !keys)) return DG_E_INVAL;
   TRY(check_version(s, version));
   dgr_engine* g = s->g;
@@ -593,10 +642,10 @@ int dgr_join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const 
     const dg_context hc = host_ctx(g, &cv);
     TRY(room_for(s, delta->n, delta_ctx->n));
     int done = 0;
-    TRY(apply_small(s, &hr, &hc, g->h_msg + o, nk, out, &done));
+    TRY(apply_small(s, &hr, &hc, g->h_msg + o, nk, out, diffs, &done));
     if (done) return DG_OK;
     TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, (o + nk) * 8));
-    return apply_delta(s, &rv, &cv, dk, nk, out, 0);
+    return apply_delta(s, &rv, &cv, dk, nk, out, diffs, 0);
   }
   TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, (o + nk) * 8));
   const dg_store* dr = &rv;
@@ -611,7 +660,18 @@ int dgr_join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const 
     TRY(dg_sort_context(g->e, &cv, &g->dctx));
     dc = &g->dctx;
   }
-  return apply_delta(s, dr, dc, dk, nk, out, 1);
+  return apply_delta(s, dr, dc, dk, nk, out, diffs, 1);
+}
+
+int dgr_join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const dg_context* delta_ctx,
+                   const uint64_t* keys, uint64_t n_keys, dgr_changed* out) {
+  return join_delta(s, version, delta, delta_ctx, keys, n_keys, out, NULL);
+}
+
+int dgr_join_delta_diffs(dgr_state* s, uint64_t version, const dg_store* delta, const dg_context* delta_ctx,
+                         const uint64_t* keys, uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs) {
+  if (!diffs) return DG_E_INVAL;
+  return join_delta(s, version, delta, delta_ctx, keys, n_keys, out, diffs);
 }
 
 typedef struct {
@@ -625,8 +685,10 @@ static int cmp_kidx(const void* a, const void* b) { /* by key, then batch order:
   return x->idx < y->idx ? -1 : x->idx > y->idx;
 }
 
-int dgr_mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
-                     const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out) {
+/* dgr_mutate_batch (diffs NULL) and dgr_mutate_batch_diffs */
+static int mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
+                        const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out,
+                        dgr_diffs* diffs) {
   if (!s || !out || (m && (!kind || !key || !val || !ts))) return DG_E_INVAL;
   TRY(check_version(s, version));
   dgr_engine* g = s->g;
@@ -682,7 +744,19 @@ int dgr_mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, 
     TRY(rc);
     break;
   }
-  return apply_delta(s, &g->mrows, &g->mctx, g->mkeys, n_keys, out, 1);
+  return apply_delta(s, &g->mrows, &g->mctx, g->mkeys, n_keys, out, diffs, 1);
+}
+
+int dgr_mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
+                     const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out) {
+  return mutate_batch(s, version, node, m, kind, key, val, ts, out, NULL);
+}
+
+int dgr_mutate_batch_diffs(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
+                           const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out,
+                           dgr_diffs* diffs) {
+  if (!diffs) return DG_E_INVAL;
+  return mutate_batch(s, version, node, m, kind, key, val, ts, out, diffs);
 }
 
 int dgr_read(dgr_state* s, uint64_t version, int all, const uint64_t* keys, uint64_t n_keys,

@@ -113,6 +113,31 @@ int dgr_join_delta(dgr_state* s, uint64_t version, const dg_store* delta, const 
 int dgr_mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
                      const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out);
 
+/* on_diffs from the resident state: for out->keys[i], read/2's value id before and after
+ * the join (old_val[i], new_val[i]; 0 where the flag is clear) and DG_DIFF_OLD | DG_DIFF_NEW
+ * presence bits (deltagpu.h dg_lww_diffs) -- what diffs_to_callback/3 compares
+ * (causal_crdt.ex:361-381; marshal.h dgm_classify_diffs turns them into adds and removes).
+ * Host views, valid until the next call on the engine. */
+typedef struct dgr_diffs {
+  uint64_t n; /* == out->n_changed; entry i describes out->keys[i] */
+  const uint64_t* old_val;
+  const uint64_t* new_val;
+  const uint8_t* flags;
+} dgr_diffs;
+
+/* dgr_join_delta / dgr_mutate_batch that also bring the changed keys' diffs home, with the
+ * same one wait: a small delta gets them from the one-launch join itself
+ * (dg_join_delta_home_diffs), a larger one from dg_join_delta_diffs, which writes them into
+ * the page-locked return block.  No old state is kept or read on the host.  Versions,
+ * DGR_E_STALE and the buffers are those of the plain calls; should the diffs of a join that
+ * applied in place not be gathered (deltagpu.h dg_join_delta_diffs), the call returns
+ * DG_E_DEVICE with the version moved on, as any failure after the device was touched. */
+int dgr_join_delta_diffs(dgr_state* s, uint64_t version, const dg_store* delta, const dg_context* delta_ctx,
+                         const uint64_t* keys, uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs);
+int dgr_mutate_batch_diffs(dgr_state* s, uint64_t version, uint32_t node, uint64_t m, const uint8_t* kind,
+                           const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out,
+                           dgr_diffs* diffs);
+
 /* read/1 (all != 0) or read/2 of `keys` (host ids, any order) (aw_lww_map.ex:211-224):
  * the winning value id per key, ascending by key id.  Host views. */
 int dgr_read(dgr_state* s, uint64_t version, int all, const uint64_t* keys, uint64_t n_keys,

@@ -52,6 +52,10 @@ DG_HOME_ROWS = DG_HOME_KEYS + 512
 DG_HOME_NODES = 2048
 DG_HOME_CTX = DG_HOME_ROWS + 4 * DG_HOME_STRIDE + DG_HOME_STRIDE // 2
 DG_HOME_WORDS = DG_HOME_CTX + DG_HOME_NODES + DG_HOME_NODES // 2
+DG_HOME_DIFF_OLD = DG_HOME_WORDS
+DG_HOME_DIFF_NEW = DG_HOME_DIFF_OLD + 512
+DG_HOME_DIFF_FLAGS = DG_HOME_DIFF_NEW + 512  # bytes from here
+DG_HOME_DIFFS_WORDS = DG_HOME_DIFF_FLAGS + 64
 
 DG_CTX_VV = 0
 DG_CTX_DOTS = 1
@@ -177,6 +181,10 @@ _SIGS = {
     "dg_join_delta_home": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
                                      C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
                                      C.POINTER(dg_store), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "dg_join_delta_home_diffs": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
+                                           C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
+                                           C.POINTER(dg_store), C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int)]),
     "dg_join_delta_rows": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
                                      C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
                                      C.POINTER(dg_store), C.c_void_p, P64, C.c_uint64, P64,

@@ -1,9 +1,10 @@
 """Host mirror of the data path of `DeltaCrdt.CausalCrdt` around the join (reference
 lib/delta_crdt/causal_crdt.ex): applying a delta to a replica's state and the diffs
 its `on_diffs` subscriber receives.  The GenServer, neighbours and sync messages are
-out of scope; the MerkleMap (aw_lww_map.merkle_map, store.MerkleTree,
-DESIGN.md §4.3), the sharded round (sharding.py, §6) and storage (storage.py, §4.6) have
-modules of their own.
+out of scope here (tests/binding_mirror.py restates the handlers over the NIF's
+mirror).  The MerkleMap (aw_lww_map.merkle_map, store.MerkleTree), the
+sharded round (sharding.py, §6) and storage (storage.py, §4.6) are in scope and have modules
+of their own.
 
     from delta_crdt_ex_amd import aw_lww_map as M, causal_crdt as CC
     st = M.compress_dots(M.new())
@@ -16,9 +17,10 @@ then diffs_to_callback/3 (:359-381) reads the changed keys on the old and on the
 state in one more (dg_read_diff) and keeps the keys whose read value changed.
 
 update_resident_state_with_delta does the same to a state that stays on the device and
-is joined in place (dg_join_delta_diffs: the join, the changed keys, the MerkleMap update
-and both reads in one call) -- the old rows are overwritten, so the reads before the join
-come out of the join itself.
+is joined in place (dg_join_delta_home_diffs for a mutation or a small sync delta, else
+dg_join_delta_diffs: the join, the changed keys, the MerkleMap update and both reads in one
+call) -- the old rows are overwritten, so the reads before the join come out of the join
+itself.
 """
 from __future__ import annotations
 
@@ -30,6 +32,9 @@ from ._abi import DG_DIFF_NEW, DG_DIFF_OLD
 from .store import Context, Store, u64
 
 
+HOME_KEYS, HOME_ROWS, HOME_CTX = 512, 512, 1024  # dg_join_delta_home's limits on the delta
+
+
 def _keyset(U, keys):
     """`keys` as (key id, key) pairs in the caller's order, and the ascending unique ids on
     the device (keys by interned id, not Python equality)."""
@@ -39,10 +44,9 @@ def _keyset(U, keys):
 
 
 def _callback_diffs(U, order, changed, old_val, new_val, flags):
-    """diffs_to_callback/3 (:361-381) from the device's reads of the changed keys: a list of
-    ("add", key, value) / ("remove", key) in `keys` order."""
-    by = {int(k): (int(f), int(o), int(n))
-          for k, o, n, f in zip(u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())}
+    """diffs_to_callback/3 (:361-381) from the device's reads of the changed keys (numpy
+    arrays): a list of ("add", key, value) / ("remove", key) in `keys` order."""
+    by = {int(k): (int(f), int(o), int(n)) for k, o, n, f in zip(changed, old_val, new_val, flags)}
     diffs = []
     for kid, k in order:
         if kid not in by:
@@ -74,7 +78,7 @@ def update_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys):
     if changed.numel() == 0:
         return new, None
     old_val, new_val, flags = eng.read_diff(state.rows, out, changed)
-    return new, _callback_diffs(U, order, changed, old_val, new_val, flags)
+    return new, _callback_diffs(U, order, u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())
 
 
 def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys, spare: Store,
@@ -98,10 +102,19 @@ def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys,
         grown = Store.empty(2 * (rows.n + delta.rows.n), rows.device)
         for f in ("key", "val", "ts", "node", "cnt"):
             setattr(spare, f, getattr(grown, f))
-    changed, old_val, new_val, flags, _ = eng.join_delta_diffs(rows, ctx, delta.rows, delta.ctx, kt,
-                                                               spare, tree)
+    home = None
+    if kt.numel() <= HOME_KEYS and delta.rows.n <= HOME_ROWS and delta.ctx.n <= HOME_CTX:
+        # a mutation or a small sync delta: the one-launch join gives the diffs too
+        # (dg_join_delta_home_diffs); None: over its other limits, nothing happened
+        home = eng.join_delta_home_diffs(rows, ctx, delta.rows, delta.ctx, kt, spare, tree)
     state._host = None
-    if changed.numel() == 0:
+    if home is not None:
+        changed, (old_val, new_val, flags) = home[0], home[4]
+    else:
+        changed, old_val, new_val, flags, _ = eng.join_delta_diffs(rows, ctx, delta.rows, delta.ctx, kt,
+                                                                   spare, tree)
+        changed, old_val, new_val, flags = u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy()
+    if len(changed) == 0:
         return None
     return _callback_diffs(U, order, changed, old_val, new_val, flags)
 

@@ -1269,10 +1269,15 @@ static_assert(SMALL_O_KEYS == DG_HOME_KEYS &&SMALL_O_ROWS == DG_HOME_ROWS && SMA
                   SMALL_O_CTX == DG_HOME_CTX && SMALL_NODES == DG_HOME_NODES && SMALL_WORDS == DG_HOME_WORDS &&
                   SMALL_FALLBACK == DG_HOME_FALLBACK,
               "the result block is the header's home layout");
+static_assert(SMALL_O_DOLD == DG_HOME_DIFF_OLD && SMALL_O_DNEW == DG_HOME_DIFF_NEW &&
+                  SMALL_O_DFLAGS == DG_HOME_DIFF_FLAGS && SMALL_DIFFS_WORDS == DG_HOME_DIFFS_WORDS &&
+                  KD_DIFF_OLD == DG_DIFF_OLD && KD_DIFF_NEW == DG_DIFF_NEW,
+              "the diff ranges behind it are the header's");
 
-int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
-                       const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
-                       dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped) {
+// dg_join_delta_home (diffs false) and dg_join_delta_home_diffs: one body, two kernels
+static int join_delta_home_impl(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                                const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                                dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped, bool diffs) {
   if (!e) return fail(DG_E_INVAL, "null engine");
   if (!swapped || !spare || !state || !state_ctx || !home)
     return fail(DG_E_INVAL, "dg_join_delta_home: null argument");
@@ -1337,7 +1342,7 @@ int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, con
   p.d_counts = e->d_counts;
   p.h_pub = e->d_pub;
   p.seq = ++e->pub_seq;
-  HIP_TRY(launch_small_delta(p, e->stream));
+  HIP_TRY(launch_small_delta(p, diffs, e->stream));
   if (copy_now) {  // the moved rows' copy into the spare (if they moved: else it returns)
     SmallTailArgs ta{};
     ta.a = rows_of(state);
@@ -1393,6 +1398,20 @@ int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, con
   state_ctx->kind = DG_CTX_VV;
   if (tree) tree->n_keys += home[7];
   return DG_OK;
+}
+
+int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                       const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                       dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped) {
+  return join_delta_home_impl(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, home, swapped,
+                              false);
+}
+
+int dg_join_delta_home_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                             const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                             dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped) {
+  return join_delta_home_impl(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, home, swapped,
+                              true);
 }
 
 static int join_delta_impl(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,

@@ -453,9 +453,15 @@ constexpr u64 SMALL_HDR = 8;
 constexpr u64 SMALL_O_KEYS = SMALL_HDR, SMALL_O_ROWS = SMALL_O_KEYS + SMALL_KEYS;
 constexpr u64 SMALL_O_CTX = SMALL_O_ROWS + 4 * (u64)SMALL_EDIT + SMALL_EDIT / 2;
 constexpr u64 SMALL_WORDS = SMALL_O_CTX + SMALL_NODES + SMALL_NODES / 2;
+// (small_delta_kernel<true>) behind the block, entry i for changed key i: read/1's
+// value id before the join, after it (SMALL_KEYS words each), and the KD_DIFF_OLD |
+// KD_DIFF_NEW presence bits (SMALL_KEYS bytes)
+constexpr u64 SMALL_O_DOLD = SMALL_WORDS, SMALL_O_DNEW = SMALL_O_DOLD + SMALL_KEYS;
+constexpr u64 SMALL_O_DFLAGS = SMALL_O_DNEW + SMALL_KEYS, SMALL_DIFFS_WORDS = SMALL_O_DFLAGS + SMALL_KEYS / 8;
 
 constexpr u32 SMALL_FALLBACK = 1u;  // flags: nothing written, the general path runs
-hipError_t launch_small_delta(const SmallArgs& p, hipStream_t st);
+// small_delta_kernel<diffs> (diffs: home has SMALL_DIFFS_WORDS)
+hipError_t launch_small_delta(const SmallArgs& p, bool diffs, hipStream_t st);
 // small.hip: the moved rows' splice copy behind the small join, one launch: blocks
 // [0, tiles) copy the state's rows outside the keyset into the spare store (when the join
 // moved rows: res[6], res[0] == 0; the small join placed the edit's rows), and the last

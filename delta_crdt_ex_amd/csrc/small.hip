@@ -434,9 +434,18 @@ __device__ __forceinline__ void tree_paths(const SmallArgs& p, SmallLds& s, bool
   SSTAMP(8);
 }
 
+// DIFFS (dg_join_delta_home_diffs): each key's thread also keeps read/1's winner of its
+// rows before and after the join -- the rule of kdelta.hip's walk: in tuple order a row wins
+// when it is the first or its ts is strictly greater -- in registers, and step 6 stores them
+// beside the changed keys.  The plain instantiation is the kernel as it was, instruction for
+// instruction: the kernel itself is the template (a body inlined into two wrappers is
+// compiled differently), and both instantiations use ONE LDS block at namespace scope (a
+// block per instantiation moves the plain kernel's register allocation).
+__shared__ SmallLds g_small_lds;
+template <bool DIFFS>
 __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   SSTAMP(0);
-  __shared__ SmallLds s;
+  SmallLds& s = g_small_lds;
   const int tid = threadIdx.x;
   const u32 nk = (u32)p.nk, nd = (u32)p.d.n, ncd = (u32)p.cd.n, ncs = (u32)p.ca.n;
   const bool dvv = p.cd.kind == 0;
@@ -591,12 +600,33 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   const bool fallback = s.flags & SMALL_FALLBACK;  // (uniform)
   // ---- 3. the join per key: kept rows, changed, distinct-key change
   u32 ne = 0, chg = 0, ja = 0, je = 0;
+  u64 ov = 0, nv = 0;  // (DIFFS) the winning value ids before and after
   if (!fallback && (u32)tid < nk) {
     const u64 k = s.key[tid];
     ja = delta_bound(s, nd, k, false);
     je = delta_bound(s, nd, k, true);
     bool c;
-    ne = merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [](const Row&) {});
+    i64 nts = 0;
+    u32 nj = 0;
+    ne = merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
+      if constexpr (DIFFS) {  // (selects, not branches: nj == 0 is "no row so far")
+        const bool w = (nj == 0) | (r.ts > nts);
+        nts = w ? r.ts : nts;
+        nv = w ? r.val : nv;
+        nj++;
+      }
+    });
+    if constexpr (DIFFS) {
+      // the state's rows as staged in LDS (read only: no write of step 6 is in sight)
+      const u32 i0 = s.aoff[tid], i1 = s.aoff[tid + 1];
+      i64 ots = 0;
+      for (u32 i = i0; i < i1; i++) {
+        const i64 t = s.at[i];
+        const bool w = (i == i0) | (t > ots);
+        ots = w ? t : ots;
+        ov = w ? s.av[i] : ov;
+      }
+    }
     chg = c ? 1u : 0u;
     s.ne[tid] = ne;
     if (ne != s.na[tid]) atomicOr(&s.moved, 1u);
@@ -699,6 +729,15 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
       if (tid == 0) p.shift[nk] = (i64)n_e - (i64)n_ak;
     }
     if (chg) home[SMALL_O_KEYS + s.coff[tid]] = s.key[tid];
+    if constexpr (DIFFS) {
+      if (chg) {  // read/1 before and after, beside the key (a value without its flag: 0)
+        const u32 o = s.coff[tid];
+        const bool had = s.na[tid] > 0, has = ne > 0;
+        home[SMALL_O_DOLD + o] = had ? ov : 0ull;
+        home[SMALL_O_DNEW + o] = has ? nv : 0ull;
+        ((uint8_t*)(home + SMALL_O_DFLAGS))[o] = (uint8_t)((had ? KD_DIFF_OLD : 0u) | (has ? KD_DIFF_NEW : 0u));
+      }
+    }
     p.a_lo[tid] = a0;
     p.a_off[tid] = s.aoff[tid];
     if (tid == 0) p.a_off[nk] = n_ak;
@@ -882,11 +921,13 @@ extern "C" int dg_debug_wave_find(const unsigned long long* a, unsigned long lon
 
 namespace dg {
 
-hipError_t launch_small_delta(const SmallArgs& p, hipStream_t st) {
-  hipLaunchKernelGGL(small_delta_kernel, dim3(1), dim3(NT), 0, st, p);
+hipError_t launch_small_delta(const SmallArgs& p, bool diffs, hipStream_t st) {
+  if (diffs)
+    hipLaunchKernelGGL(small_delta_kernel<true>, dim3(1), dim3(NT), 0, st, p);
+  else
+    hipLaunchKernelGGL(small_delta_kernel<false>, dim3(1), dim3(NT), 0, st, p);
   return hipGetLastError();
 }
-
 
 hipError_t launch_small_tail(const SmallTailArgs& p, hipStream_t st) {
   hipLaunchKernelGGL(small_tail_kernel, dim3((unsigned)(p.tiles ? p.tiles : 1)), dim3(NT), 0, st, p);

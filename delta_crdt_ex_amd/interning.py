@@ -231,6 +231,13 @@ class Universe:
         self.terms_version += 1
         return vid
 
+    def value_find(self, t):
+        """The id `t` has as a value WITHOUT interning it (marshal.h dgm_value_find): None
+        when it was never interned, so no row can hold it."""
+        if is_canonical_int(t):
+            return int(t) + (1 << 62)
+        return self._val_id.get(_hkey(t))
+
     def _gap_id(self, p: int, low: bool):
         """An id strictly between the neighbours of insertion point p inside the value's
         region (LOW or HIGH, exclusive bounds), or None when the gap is used up."""

@@ -10,6 +10,8 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
     state_load(engine, dots, value)                 -> ("ok", state, version)
     join_delta(state, version, dots, value, keys)   -> ("ok", version', new_dots, changed)
     mutate_batch(state, version, node, ops)         -> ("ok", version', new_dots, changed)
+    join_delta_diffs(state, version, dots, value, keys)
+    mutate_batch_diffs(state, version, node, ops)   -> ("ok", version', new_dots, changed, diffs)
     read(state, version, keys | "all")              -> ("ok", {key: value})
     take(state, version, keys)                      -> ("ok", value_map)
     merkle_build(state, version, depth)             -> "ok"
@@ -27,6 +29,12 @@ frozenset of (node, counter), a compressed context a {node: max} dict, a value m
 {key: {(value, ts): frozenset(dots)}}, nil None.  An engine may be opened with `wrap` /
 `unwrap` functions applied to every term crossing it (the tests keep their terms in an
 exact-equality form, as BEAM maps compare keys, and pass the conversions).
+
+`diffs` is what on_diffs receives (diffs_to_callback/3, causal_crdt.ex:361-381), computed
+from the device's reads of the changed keys before and after the join -- no old struct is
+read: [("add", key, value) | ("remove", key)] in ascending key-id order, the order of
+`changed`.  The reference emits them in the order of its `keys` argument; a consumer must
+not rely on the order inside one callback list.
 
 Interning is the NIF's (c_src/marshal.c), mirrored by interning.Universe with the same
 ids: key ids are hashes, value ids order-preserving, node ids dense; a relabel rewrites
@@ -48,6 +56,11 @@ LIB_PATH = os.path.join(ROOT, "c_src", "_build", "libdgreplica.so")
 
 DGR_E_STALE = -16
 U64_MAX = (1 << 64) - 1
+
+
+class dgr_diffs(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("old_val", C.c_void_p), ("new_val", C.c_void_p),
+                ("flags", C.c_void_p)]
 
 
 class dgr_changed(C.Structure):
@@ -73,6 +86,10 @@ _SIGS = {
     "dgr_join_delta": (I32, [VP, U64, C.POINTER(dg_store), C.POINTER(dg_context), VP, U64,
                              C.POINTER(dgr_changed)]),
     "dgr_mutate_batch": (I32, [VP, U64, C.c_uint32, U64, VP, VP, VP, VP, C.POINTER(dgr_changed)]),
+    "dgr_join_delta_diffs": (I32, [VP, U64, C.POINTER(dg_store), C.POINTER(dg_context), VP, U64,
+                                   C.POINTER(dgr_changed), C.POINTER(dgr_diffs)]),
+    "dgr_mutate_batch_diffs": (I32, [VP, U64, C.c_uint32, U64, VP, VP, VP, VP, C.POINTER(dgr_changed),
+                                     C.POINTER(dgr_diffs)]),
     "dgr_read": (I32, [VP, U64, I32, VP, U64, C.POINTER(VP), C.POINTER(VP), PU64]),
     "dgr_take": (I32, [VP, U64, VP, U64, C.POINTER(dg_store)]),
     "dgr_merkle_build": (I32, [VP, U64, C.c_uint32]),
@@ -325,6 +342,41 @@ def _changed_result(eng: Engine, ch: dgr_changed):
     return ("ok", int(ch.version), dots, changed)
 
 
+DIFF_NONE, DIFF_ADD, DIFF_REMOVE = 0, 1, 2
+
+
+def classify_diffs(old_val, new_val, flags, nil_id):
+    """marshal.h dgm_classify_diffs: diffs_to_callback/3's case (causal_crdt.ex:368-374)
+    over value ids -- per entry DIFF_NONE, DIFF_ADD or DIFF_REMOVE.  A side is absent when
+    its flag is clear or its id is nil's (`nil_id`, None when nil was never interned)."""
+    kind = []
+    for o, n, f in zip(old_val, new_val, flags):
+        has_o = bool(int(f) & _abi.DG_DIFF_OLD) and not (nil_id is not None and int(o) == nil_id)
+        has_n = bool(int(f) & _abi.DG_DIFF_NEW) and not (nil_id is not None and int(n) == nil_id)
+        if not has_n:
+            kind.append(DIFF_REMOVE if has_o else DIFF_NONE)
+        else:
+            kind.append(DIFF_NONE if has_o and int(o) == int(n) else DIFF_ADD)
+    return kind
+
+
+def _diffs_result(eng: Engine, ch: dgr_changed, df: dgr_diffs):
+    res = _changed_result(eng, ch)
+    n = int(df.n)
+    keys = _arr(ch.keys, n, np.uint64)
+    ov, nv = _arr(df.old_val, n, np.uint64), _arr(df.new_val, n, np.uint64)
+    fl = (np.ctypeslib.as_array(C.cast(df.flags, C.POINTER(C.c_uint8)), shape=(n,)).copy()
+          if n else np.zeros(0, np.uint8))
+    U, w = eng.universe, eng.wrap
+    diffs = []
+    for kid, v, kind in zip(keys, nv, classify_diffs(ov, nv, fl, U.value_find(None))):
+        if kind == DIFF_ADD:
+            diffs.append(("add", w(U.key_term(int(kid))), _value_term(eng, v)))
+        elif kind == DIFF_REMOVE:
+            diffs.append(("remove", w(U.key_term(int(kid)))))
+    return res + (diffs,)
+
+
 # ------------------------------------------------------------------ the NIFs
 def engine_open(device: int = 0, wrap=None, unwrap=None):
     return ("ok", Engine(device, wrap, unwrap))
@@ -344,7 +396,7 @@ def state_load(engine: Engine, dots, value):
     return ("ok", s, s.version)
 
 
-def join_delta(state: State, version: int, dots, value, keys):
+def join_delta(state: State, version: int, dots, value, keys, _diffs: bool = False):
     eng = state.engine
     h = _Rows()
     _marshal_dots(eng, dots, h)
@@ -356,6 +408,11 @@ def join_delta(state: State, version: int, dots, value, keys):
             return _err(rc)
     st, cx = h.store(), h.context()
     ch = dgr_changed()
+    if _diffs:
+        df = dgr_diffs()
+        rc = eng.lib.dgr_join_delta_diffs(state.ptr, version, C.byref(st), C.byref(cx), kid.ctypes.data,
+                                          len(kid), C.byref(ch), C.byref(df))
+        return _err(rc) if rc else _diffs_result(eng, ch, df)
     rc = eng.lib.dgr_join_delta(state.ptr, version, C.byref(st), C.byref(cx), kid.ctypes.data,
                                 len(kid), C.byref(ch))
     if rc:
@@ -363,7 +420,13 @@ def join_delta(state: State, version: int, dots, value, keys):
     return _changed_result(eng, ch)
 
 
-def mutate_batch(state: State, version: int, node, ops):
+def join_delta_diffs(state: State, version: int, dots, value, keys):
+    """join_delta that also returns on_diffs' list, from the device's reads of the changed
+    keys before and after the join (dgr_join_delta_diffs): no old struct is read."""
+    return join_delta(state, version, dots, value, keys, _diffs=True)
+
+
+def mutate_batch(state: State, version: int, node, ops, _diffs: bool = False):
     """ops = [("add", key, value, ts) | ("remove", key)] in the order they were made"""
     eng = state.engine
     U, un = eng.universe, eng.unwrap
@@ -389,11 +452,22 @@ def mutate_batch(state: State, version: int, node, ops):
         if rc:
             return _err(rc)
     ch = dgr_changed()
+    if _diffs:
+        df = dgr_diffs()
+        rc = eng.lib.dgr_mutate_batch_diffs(state.ptr, version, nid, m, kind.ctypes.data, key.ctypes.data,
+                                            val.ctypes.data, ts.ctypes.data, C.byref(ch), C.byref(df))
+        return _err(rc) if rc else _diffs_result(eng, ch, df)
     rc = eng.lib.dgr_mutate_batch(state.ptr, version, nid, m, kind.ctypes.data, key.ctypes.data,
                                   val.ctypes.data, ts.ctypes.data, C.byref(ch))
     if rc:
         return _err(rc)
     return _changed_result(eng, ch)
+
+
+def mutate_batch_diffs(state: State, version: int, node, ops):
+    """mutate_batch that also returns on_diffs' list for the batch's net changes
+    (dgr_mutate_batch_diffs)."""
+    return mutate_batch(state, version, node, ops, _diffs=True)
 
 
 def read(state: State, version: int, keys):
@@ -478,6 +552,7 @@ def resolve_keys(engine: Engine, keys):
     return out
 
 
-__all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "read", "take",
+__all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "join_delta_diffs",
+           "mutate_batch_diffs", "classify_diffs", "read", "take",
            "merkle_build", "merkle_prepare", "merkle_continue", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

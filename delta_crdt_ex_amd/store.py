@@ -736,26 +736,33 @@ class Engine:
             return changed[:nch], None, None, None, bool(sw.value)
         return changed[:nch], ov[:nch], nv[:nch], fl[:nch], bool(sw.value)
 
+    def home_block(self):
+        """The page-locked result block of join_delta_home / join_delta_home_diffs as a numpy
+        view (DG_HOME_DIFFS_WORDS words; the plain call writes a prefix of it)."""
+        if getattr(self, "_home", None) is None:
+            p = C.c_void_p()
+            check(self.lib.dg_host_alloc(self.h, _abi.DG_HOME_DIFFS_WORDS * 8, C.byref(p)))
+            self._home = p
+        return np.ctypeslib.as_array(C.cast(self._home, C.POINTER(C.c_uint64)),
+                                     shape=(_abi.DG_HOME_DIFFS_WORDS,))
+
     def join_delta_home(self, state: Store, state_ctx: Context, delta: Store, delta_ctx: Context,
-                        keys: torch.Tensor, spare: Store, tree: MerkleTree | None = None):
+                        keys: torch.Tensor, spare: Store, tree: MerkleTree | None = None,
+                        _diffs: bool = False):
         """dg_join_delta_home: join_delta for a small delta in one launch chain with one
         host wait, the result (changed keys, their rows, the new context) written into
         page-locked host memory.  Returns None when the library declined (DG_HOME_FALLBACK:
         nothing happened), else (changed keys, rows (key, val, ts, node, cnt), context
         (node, cnt), swapped) as numpy arrays."""
         self._order()
-        if getattr(self, "_home", None) is None:
-            p = C.c_void_p()
-            check(self.lib.dg_host_alloc(self.h, _abi.DG_HOME_WORDS * 8, C.byref(p)))
-            self._home = p
+        h = self.home_block()
         ss, sc, sd, cd, sp = state.abi(), state_ctx.abi(), delta.abi(), delta_ctx.abi(), spare.abi()
         t = tree.abi() if tree is not None else None
         kp, nk = self._keys(keys)
         sw = C.c_int(0)
-        check(self.lib.dg_join_delta_home(self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp,
-                                          nk, C.byref(sp), C.byref(t) if t is not None else None,
-                                          self._home, C.byref(sw)))
-        h = np.ctypeslib.as_array(C.cast(self._home, C.POINTER(C.c_uint64)), shape=(_abi.DG_HOME_WORDS,))
+        f = self.lib.dg_join_delta_home_diffs if _diffs else self.lib.dg_join_delta_home
+        check(f(self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp),
+                C.byref(t) if t is not None else None, self._home, C.byref(sw)))
         if int(h[0]) & _abi.DG_HOME_FALLBACK:
             return None
         nch, nr, nc = int(h[1]), int(h[2]), int(h[3])
@@ -780,6 +787,21 @@ class Engine:
             tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
             tree.store = state
         return keys_out, rows, ctx, bool(sw.value)
+
+    def join_delta_home_diffs(self, state: Store, state_ctx: Context, delta: Store, delta_ctx: Context,
+                              keys: torch.Tensor, spare: Store, tree: MerkleTree | None = None):
+        """dg_join_delta_home_diffs: join_delta_home plus, for every changed key, its LWW read
+        before and after the join out of the same launch and wait (what on_diffs compares).
+        None when the library declined, else join_delta_home's tuple followed by (old_val,
+        new_val, flags): value ids (0 where the flag is clear) and DG_DIFF_OLD | DG_DIFF_NEW
+        bits, entry i describing changed key i."""
+        r = self.join_delta_home(state, state_ctx, delta, delta_ctx, keys, spare, tree, _diffs=True)
+        if r is None:
+            return None
+        h, n = self.home_block(), len(r[0])
+        fl = h[_abi.DG_HOME_DIFF_FLAGS:_abi.DG_HOME_DIFFS_WORDS].view(np.uint8)[:n].copy()
+        return r + ((h[_abi.DG_HOME_DIFF_OLD:_abi.DG_HOME_DIFF_OLD + n].copy(),
+                     h[_abi.DG_HOME_DIFF_NEW:_abi.DG_HOME_DIFF_NEW + n].copy(), fl),)
 
     def merkle_update(self, tree: MerkleTree, new: Store, keys: torch.Tensor) -> MerkleTree:
         """MerkleMap.put/delete of the changed `keys` + update_hashes: `tree` indexed

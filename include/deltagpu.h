@@ -357,6 +357,20 @@ int dg_join_delta_home(dg_engine* e, dg_store* state, dg_context* state_ctx, con
                        const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
                        dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped);
 
+/* dg_join_delta_home plus, for the changed key home[DG_HOME_KEYS + i], its LWW read before
+ * and after the join (as dg_lww_diffs describes them) in entry i of three ranges behind the
+ * block: `home` is DG_HOME_DIFFS_WORDS words from dg_host_alloc, words [0, DG_HOME_WORDS)
+ * are what dg_join_delta_home writes, and the winners come out of the same kernel's walk of
+ * each key, behind the same ONE wait.  Limits, DG_HOME_FALLBACK (the three ranges are then
+ * not written either), *swapped and the error behaviour are dg_join_delta_home's. */
+#define DG_HOME_DIFF_OLD DG_HOME_WORDS               /* 512 words: old value ids */
+#define DG_HOME_DIFF_NEW (DG_HOME_DIFF_OLD + 512)    /* 512 words: new value ids */
+#define DG_HOME_DIFF_FLAGS (DG_HOME_DIFF_NEW + 512)  /* 512 BYTES: DG_DIFF_OLD | DG_DIFF_NEW */
+#define DG_HOME_DIFFS_WORDS (DG_HOME_DIFF_FLAGS + 64)
+int dg_join_delta_home_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
+                             const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
+                             dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped);
+
 /* Fold of join/3 over k stores (how CausalCrdt applies k deltas in a row,
  * causal_crdt.ex:86-89,383-384): out = join(...join(join(s0, s1), s2)..., s_{k-1})
  * over all keys.  A row survives iff for every input i it is present in s_i or its
