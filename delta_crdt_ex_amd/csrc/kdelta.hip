@@ -325,7 +325,10 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
   }
   // the tree's put/delete right away (all or nothing: a guard or an input error found
   // later makes the host undo it, merkle.hip kd_tree_kernel with the opposite sign)
-  if (p.has_tree) tree_put(p, u < p.nk && !big, k, chg, dh, (int)ne - (int)na);
+  // (a key over KD_RUN keeps its bucket and chunk as its segment, with nothing to add, as in
+  // the undo: were its lane left out, the keys of one bucket or chunk on either side of it
+  // would be two runs of lanes, and the second run's sum takes the first's in again)
+  if (p.has_tree) tree_put(p, u < p.nk, k, chg && !big, dh, (int)ne - (int)na);
   KDSTAMP(2, 5);
   v[0] = na;
   v[1] = ne;

@@ -511,9 +511,30 @@ def _keys_with_runs(rng, n, prefix_bits=0, prefix=0):
     u = np.unique(rng.integers(0, 1 << 63, n, dtype=np.uint64) >> np.uint64(prefix_bits))
     if prefix_bits:
         u = u | np.uint64(prefix << (64 - prefix_bits))
+    return _repeat_keys(rng, u, n), u
+
+
+def _repeat_keys(rng, u, n):
+    """The first n rows of the ascending keys u, each repeated one to three times."""
     reps = rng.choice([1, 1, 1, 2, 3], len(u))
-    a = np.repeat(u, reps)[:n]
-    return a, u
+    return np.repeat(u, reps)[:n]
+
+
+SMALL_TAKEN = 1024  # csrc/dg_launch.h: wave_find stops counting a run once it is past this
+
+
+def _check_wave_find(a, what):
+    """Every key of a, every key + 1 and three fixed keys: first row and run against
+    np.searchsorted (a run of more than SMALL_TAKEN rows: reported as more than that)."""
+    n = len(a)
+    q = np.concatenate([np.unique(a), (np.unique(a) + np.uint64(1)) if n else a,
+                        np.array([0, (1 << 64) - 1, 5 << 61], np.uint64)])
+    lo, run = _wave_find(a, q)
+    want_lo = np.searchsorted(a, q, side="left")
+    want_run = np.searchsorted(a, q, side="right") - want_lo
+    run_ok = np.where(want_run <= SMALL_TAKEN, run == want_run, run > SMALL_TAKEN)
+    bad = np.nonzero((lo != want_lo) | ~run_ok)[0]
+    assert len(bad) == 0, (what, len(bad), q[bad[:4]], lo[bad[:4]], want_lo[bad[:4]], run[bad[:4]])
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 10_000, 1 << 20, (1 << 20) + 1, 1_060_000, 1040 ** 2 - 1,
@@ -523,13 +544,28 @@ def test_wave_find_matches_searchsorted(n, prefix_bits):
     rng = np.random.default_rng(n + prefix_bits)
     a, u = _keys_with_runs(rng, n, prefix_bits, 5)
     assert len(a) == n
-    q = np.concatenate([np.unique(a), (np.unique(a) + np.uint64(1)) if n else a,
-                        np.array([0, (1 << 64) - 1, 5 << 61], np.uint64)])
-    lo, run = _wave_find(a, q)
-    want_lo = np.searchsorted(a, q, side="left")
-    want_run = np.searchsorted(a, q, side="right") - want_lo
-    bad = np.nonzero((lo != want_lo) | (run != want_run))[0]
-    assert len(bad) == 0, (n, prefix_bits, len(bad), q[bad[:4]], lo[bad[:4]], want_lo[bad[:4]], run[bad[:4]])
+    _check_wave_find(a, (n, prefix_bits))
+
+
+@pytest.mark.parametrize("n", [10_000, 1_060_000])
+@pytest.mark.parametrize("name", ["geometric", "two_clusters", "dense_plus_max"])
+def test_wave_find_skewed_keys(name, n):
+    """Keys that are not uniform hashes: the first probe (k / 2^64 of the way) is nowhere
+    near, so the 64-ary rounds start from a whole side of the store (tests/skew.py)."""
+    import skew
+    rng = np.random.default_rng(n)
+    a = _repeat_keys(rng, skew.GENERATORS[name](rng, n), n)
+    assert len(a) == n
+    _check_wave_find(a, (name, n))
+
+
+def test_wave_find_hot_key():
+    """Hashed keys, one of them with 20,000 rows: the run is cut off past SMALL_TAKEN."""
+    import skew
+    st, hot = skew.hot_state()
+    a = st["rows"][0]
+    assert int((a == hot).sum()) > SMALL_TAKEN
+    _check_wave_find(a, "hot key")
 
 
 def _unique_key_state(rng, n, prefix_bits=0, prefix=0):

@@ -209,6 +209,73 @@ def test_read_lww_run_lengths(engine, shape):
     assert np.array_equal(u64(ok), wk) and np.array_equal(u64(ov), wv)
 
 
+# ------------------------------------------------------------------ dg_take_keys, long runs
+# take_keys_kernel maps a 256-key tile's output rows to their keys through LDS while the
+# tile takes at most 1024 rows (TAKE_TILE, MAPCAP in csrc/take.hip); past that every output
+# row binary-searches the tile's offsets.
+
+TAKE_RUNS = np.array([1, 2, 3, 4, 5, 7, 8, 9, 12, 13], np.int64)
+
+
+def _kt(keys):
+    return torch.from_numpy(np.ascontiguousarray(keys, np.uint64).view(np.int64)).to(DEV)
+
+
+def _check_take(engine, rows, s, ks):
+    got = engine.take_keys(s, _kt(ks))
+    sel = np.isin(rows[0], ks)
+    assert got.n == int(sel.sum())
+    rows_eq(got, tuple(c[sel] for c in rows))
+    return sel
+
+
+def _tile_rows(rows, ks):
+    """Rows each 256-key tile of the key list takes."""
+    ukeys, cnt = np.unique(rows[0], return_counts=True)
+    pos = np.searchsorted(ukeys, ks)
+    hit = ukeys[np.minimum(pos, len(ukeys) - 1)] == ks
+    per_key = np.where(hit, cnt[np.minimum(pos, len(ukeys) - 1)], 0)
+    return [int(per_key[t:t + 256].sum()) for t in range(0, len(ks), 256)]
+
+
+def test_take_keys_tiles_past_the_lds_map(engine):
+    """600 keys of 1..13 rows: tiles 0 and 1 take about 1,640 rows each (searched offsets),
+    tile 2 takes 88 keys' (mapped).  Then with every third key -- and each tile's first and
+    last -- replaced by an absent one, so empty ranges share an offset with their
+    neighbours; the searching tiles still take more than 1024 rows."""
+    rng = np.random.default_rng(17)
+    rows = runs_store(rng, TAKE_RUNS[np.arange(600) % 10], ts_range=3)
+    s = Store.from_numpy(*rows, device=DEV)
+    keys = np.unique(rows[0])
+    assert len(keys) == 600
+    per_tile = _tile_rows(rows, keys)
+    assert per_tile[0] > 1024 and per_tile[1] > 1024 and per_tile[2] <= 1024
+    assert _check_take(engine, rows, s, keys).all()
+    gone = np.unique(np.concatenate([np.arange(0, 600, 3), [0, 255, 256, 511, 512, 599]]))
+    ks = keys.copy()
+    ks[gone] = keys[gone] + np.uint64(1)
+    assert bool(np.all(ks[1:] > ks[:-1])) and not np.isin(ks[gone], keys).any()
+    per_tile = _tile_rows(rows, ks)
+    assert per_tile[0] > 1024 and per_tile[1] > 1024 and 0 < per_tile[2] <= 1024
+    _check_take(engine, rows, s, ks)
+
+
+@pytest.mark.parametrize("n_keys,last_run", [(594, 4), (597, 8)])
+def test_take_keys_last_run_ends_the_store(engine, n_keys, last_run):
+    """The last key's run is exactly 4 / 8 rows and ends at the store's last row: the
+    four-rows-a-round walk reaches s.n on a full round (its end clamp)."""
+    rng = np.random.default_rng(n_keys)
+    lens = TAKE_RUNS[np.arange(n_keys) % 10]
+    assert lens[-1] == last_run
+    rows = runs_store(rng, lens, ts_range=3)
+    s = Store.from_numpy(*rows, device=DEV)
+    keys = np.unique(rows[0])
+    assert int((rows[0] == keys[-1]).sum()) == last_run and rows[0][-1] == keys[-1]
+    assert _check_take(engine, rows, s, keys).all()
+    assert int(_check_take(engine, rows, s, keys[-1:]).sum()) == last_run
+    _check_take(engine, rows, s, np.array([keys[0], keys[-1], keys[-1] + np.uint64(1)], np.uint64))
+
+
 def test_read_lww_config2(engine):
     a, b = W.config2()
     rows, _ = R.join2(a["rows"], a["ctx"], b["rows"], b["ctx"])
@@ -372,3 +439,113 @@ def test_remap_values_region_local(engine):
     with pytest.raises(DeltaGpuError):  # rows hold (1 << 60) -+ 100: inside, not in the table
         engine.remap_values(s, np.array([(1 << 60) - 200, (1 << 60) + 200], np.uint64),
                             np.array([(1 << 60) - 300, (1 << 60) + 300], np.uint64))
+
+
+@pytest.mark.parametrize("n_ids,n_rows", [(2047, 10_000), (2048, 10_000), (2049, 10_000), (5000, 10_000),
+                                          (2049, 0), (2049, 1), (2049, 1023), (2049, 1025)])
+def test_remap_values_table_sizes(engine, n_ids, n_rows):
+    """Id tables at, below and above the 2048 entries remap_values_kernel stages in LDS
+    (larger ones are searched in global memory): rows holding table ids (the first and last
+    among them), ids below and above the region and canonical integers, against a numpy
+    lookup; and an id inside the region that the table lacks is refused."""
+    from delta_crdt_ex_amd._abi import DeltaGpuError
+    rng = np.random.default_rng(n_ids + n_rows)
+    old = np.uint64(1 << 40) + np.cumsum(rng.integers(2, 10, n_ids)).astype(np.uint64)
+    new = old[0] + np.arange(n_ids, dtype=np.uint64) * np.uint64(2)  # ascending, inside the region
+    assert bool(np.all(old[1:] > old[:-1])) and new[-1] <= old[-1]
+
+    def store_of(val):
+        n = len(val)
+        key = (np.arange(n) // 50).astype(np.uint64)
+        o = np.lexsort((val, key))
+        rows = (key, val[o], np.zeros(n, np.int64), np.zeros(n, np.uint32), np.arange(1, n + 1, dtype=np.uint64))
+        return rows, Store.from_numpy(*rows, device=DEV)
+
+    outside = np.array([0, 5, old[0] - np.uint64(1), old[-1] + np.uint64(1), 1 << 57], np.uint64)
+    pool = np.concatenate([old[rng.integers(0, n_ids, 4 * n_rows // 10)], outside[rng.integers(0, 5, 3 * n_rows // 10)],
+                           rng.integers(1 << 58, 1 << 63, n_rows, dtype=np.uint64)])[:max(n_rows - 2, 0)]
+    val = rng.permutation(np.concatenate([pool, old[[0, -1]]]))[:n_rows]
+    rows, s = store_of(val)
+    assert s.n == n_rows
+    engine.remap_values(s, old, new)
+    v = rows[1]
+    j = np.minimum(np.searchsorted(old, v), n_ids - 1)
+    want = np.where(old[j] == v, new[j], v)
+    if n_rows >= 1000:
+        assert (want != v).sum() > n_rows // 4 and (want == v).sum() > n_rows // 4
+    assert np.array_equal(s.to_numpy()[1], want)
+    engine.store_check(s)
+    if n_ids == 5000 and n_rows:
+        stale = old[n_ids // 2] + np.uint64(1)  # (the gaps are at least 2)
+        assert stale not in old
+        bad = val.copy()
+        bad[n_rows // 3] = stale
+        _, sb = store_of(bad)
+        with pytest.raises(DeltaGpuError):
+            engine.remap_values(sb, old, new)
+
+
+# ------------------------------------------------------------------ dg_sort_store, large and degenerate
+# digit_scan_kernel scans a digit's tile counts 256 tiles a round and carries between the
+# rounds (more than 1,048,576 rows); sort_scan_kernel likewise past 1024 tiles (4,194,304 rows).
+
+@pytest.mark.parametrize("n,dups", [(4096, 0), (4096, 1000), (8192, 0), (8192, 1000), (1_048_576, 0),
+                                    (1_048_576, 1000), (1_048_577, 1000), (4_194_305, 1000)])
+def test_sort_store_large(engine, n, dups):
+    """Rows in order by construction (ascending keys, val = the row's rank; ts of both
+    signs, node and cnt random, so every byte pass runs), shuffled, with `dups` rows
+    repeated at the end: n an exact multiple of the 4096-row tile, one past 256 tiles, one
+    past 1024 tiles."""
+    rng = np.random.default_rng(n + dups)
+    want = (np.sort(rng.integers(0, 1 << 64, n, dtype=np.uint64)), np.arange(n, dtype=np.uint64),
+            rng.integers(-(1 << 63), (1 << 63) - 1, n, dtype=np.int64),
+            rng.integers(0, 1 << 32, n, dtype=np.uint32), rng.integers(0, 1 << 64, n, dtype=np.uint64))
+    order = np.concatenate([rng.permutation(n), rng.integers(0, n, dups)])
+    s = Store.from_numpy(*(c[order] for c in want), device=DEV)
+    assert s.n == n + dups
+    got = engine.sort_store(s)
+    rows_eq(got, want)
+    engine.store_check(got)
+
+
+@pytest.mark.parametrize("case", ["only key varies", "only ts varies", "only cnt's low byte, in order",
+                                  "identical rows"])
+def test_sort_store_skipped_passes(engine, case):
+    """Fields whose every byte is constant: all of their passes are skipped, and the
+    identity order (no index array yet) is carried into the next field."""
+    rng = np.random.default_rng(len(case))
+    n = 5000
+    key, val = np.full(n, 0x1234567890ABCDEF, np.uint64), np.full(n, 1 << 62, np.uint64)
+    ts, node, cnt = np.full(n, -5, np.int64), np.full(n, 3, np.uint32), np.full(n, 77, np.uint64)
+    if case == "only key varies":
+        key = rng.integers(0, 1 << 64, n, dtype=np.uint64)
+    elif case == "only ts varies":
+        ts = rng.integers(-(1 << 40), 1 << 40, n).astype(np.int64)
+        assert (ts < 0).any() and (ts > 0).any()
+    elif case == "only cnt's low byte, in order":
+        cnt = np.sort(rng.integers(0, 256, n)).astype(np.uint64)
+    rows = (key, val, ts, node, cnt)
+    want = _np_sorted_unique(rows)
+    assert len(want[0]) == {"only key varies": n, "only ts varies": n, "only cnt's low byte, in order": 256,
+                            "identical rows": 1}[case]
+    got = engine.sort_store(Store.from_numpy(*rows, device=DEV))
+    rows_eq(got, want)
+    engine.store_check(got)
+
+
+def test_sort_context_vv_and_large_dot_list(engine):
+    """dg_sort_context of a VV (3,000 distinct nodes, reversed: one field) and of a dot list
+    of 1,048,577 distinct pairs (one past 256 tiles), shuffled."""
+    nodes = np.arange(3000, dtype=np.uint32) * np.uint32(7) + np.uint32(1)
+    cnts = np.arange(3000, dtype=np.uint64) ** 2 + np.uint64(1)
+    got = engine.sort_context(Context.from_numpy(W.VV, nodes[::-1].copy(), cnts[::-1].copy(), DEV))
+    ctx_eq(got, (W.VV, nodes, cnts))
+    rng = np.random.default_rng(8)
+    n = 1_048_577
+    node = rng.integers(0, 70, n).astype(np.uint32)
+    cnt = np.arange(n, dtype=np.uint64) * np.uint64(1 << 20) + rng.integers(0, 1 << 20, n).astype(np.uint64)
+    perm = rng.permutation(n)
+    node, cnt = node[perm], cnt[perm]
+    got = engine.sort_context(Context.from_numpy(W.DOTS, node, cnt, DEV))
+    o = np.lexsort((cnt, node))
+    ctx_eq(got, (W.DOTS, node[o], cnt[o]))
