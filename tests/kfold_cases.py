@@ -16,12 +16,19 @@ def _sort_order(key, val, ts, node, cnt):
 
 def random_fold(seed, n_keys=2000, k=8, n_nodes=12, rows_per_key=3, hashed=True, node_base=0,
                 ctx_node_max=None, dots_ctx=False, p_state=0.6, p_keys=0.06, p_take=0.5,
-                p_outside=0.01, p_full=0.0, delta_dots=False):
+                p_outside=0.01, p_full=0.0, delta_dots=False, keys=None):
     """dots_ctx: every context a dot set (the state's too); delta_dots: the deltas'
-    contexts dot sets (MapSet deltas, aw_lww_map.ex:124-146), the state's a VV."""
+    contexts dot sets (MapSet deltas, aw_lww_map.ex:124-146), the state's a VV.  keys: the
+    distinct key ids themselves (n_keys = their number; tests/kfold_plan.py places keys in
+    chosen buckets); no draw depends on them, so a seed's other columns stay what they are."""
     rng = np.random.default_rng(seed)
-    ids = np.arange(1, n_keys + 1, dtype=np.uint64)
-    keys = splitmix64_np(ids) if hashed else ids
+    if keys is None:
+        ids = np.arange(1, n_keys + 1, dtype=np.uint64)
+        keys = splitmix64_np(ids) if hashed else ids
+    else:
+        keys = np.asarray(keys, np.uint64)
+        n_keys = len(keys)
+        assert len(np.unique(keys)) == n_keys
     nr = rng.integers(1, rows_per_key + 1, n_keys)
     E = int(nr.sum())
     kidx = np.repeat(np.arange(n_keys), nr)
