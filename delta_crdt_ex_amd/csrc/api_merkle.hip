@@ -1,0 +1,320 @@
+// api_merkle.hip — the Merkle calls of the C-ABI: build, update, diff and the
+// continuation protocol.
+#include "dg_engine.h"
+
+namespace {
+
+// one full diff enqueued: the group sums of this call and the ones its write kernel zeroes
+// (all g words: a call of another depth may have dirtied more groups than this one has)
+hipError_t enqueue_merkle_diff(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
+                               const dg_store* sb, uint64_t* out_keys, uint64_t cap, u64* d_total) {
+  const u64 g = e->diff_bsum.cap;
+  u64* use = e->diff_bsum.as<u64>() + (e->diff_parity ? g : 0);
+  u64* zero = e->diff_bsum.as<u64>() + (e->diff_parity ? 0 : g);
+  e->diff_parity ^= 1;
+  return launch_merkle_diff(merkle_of(a), rows_of(sa), merkle_of(b), rows_of(sb), out_keys, cap,
+                            e->tmp.as<u64>(), use, zero, g, d_total, e->stream);
+}
+
+int same_tree_shape(const dg_merkle* a, const dg_merkle* b, const char* what) {
+  if (a->depth != b->depth || a->shard_bits != b->shard_bits || a->shard != b->shard)
+    return fail(DG_E_INVAL, "%s: trees of different shape (depth %u/%u, shard %llu/%llu)", what,
+                a->depth, b->depth, (unsigned long long)a->shard, (unsigned long long)b->shard);
+  return DG_OK;
+}
+
+}  // namespace
+
+// The build's launch, shared by the synchronous call, the asynchronous one and the replay.
+int merkle_build_enqueue(dg_engine* e, const dg_store* s, dg_merkle* t, uint64_t* d_n_keys) {
+  TRY(check_store(s, "dg_merkle_build"));
+  TRY(check_merkle(t, "dg_merkle_build"));
+  if (!d_n_keys) return fail(DG_E_INVAL, "dg_merkle_build: null d_n_keys");
+  TRY(set_device(e));
+  TRY(ensure_tmp(e, merkle_ctr_words(t->depth) * sizeof(u32)));
+  HIP_TRY(hipMemsetAsync(e->ticket + TK_INPUT, 0, sizeof(u32), e->stream));
+  HIP_TRY(launch_merkle_build(rows_of(s), merkle_of(t), d_n_keys, e->ticket + MERKLE_ARRIVE,
+                              e->tmp.as<u64>(), e->ticket + TK_INPUT, e->stream));
+  return DG_OK;
+}
+
+extern "C" {
+
+int dg_merkle_build_async(dg_engine* e, const dg_store* s, dg_merkle* t, uint64_t* d_n_keys) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  if (e->pending.size() >= MAX_PENDING) TRY(dg_engine_sync(e));
+  TRY(merkle_build_enqueue(e, s, t, d_n_keys));
+  dg_engine::Pending q{};
+  q.kind = 1;
+  q.a = *s;
+  q.t = *t;
+  q.tp = t;
+  q.d_counts = d_n_keys;
+  e->pending.push_back(q);
+  return DG_OK;
+}
+
+int dg_merkle_build(dg_engine* e, const dg_store* s, dg_merkle* t) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(settle(e));
+  TRY(merkle_build_enqueue(e, s, t, e->d_counts));  // not logged: it is settled right here
+  TRY(read_counts(e));
+  TRY(tree_input_error(e->h_ticket[TK_INPUT], "dg_merkle_build"));
+  t->n_keys = e->h_counts[JC_ROWS];
+  return DG_OK;
+}
+
+int dg_merkle_update(dg_engine* e, dg_merkle* t, const dg_store* old_s, const dg_store* new_s,
+                     const uint64_t* keys, uint64_t n_keys) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(t, "dg_merkle_update"));
+  TRY(check_store(old_s, "dg_merkle_update old"));
+  TRY(check_store(new_s, "dg_merkle_update new"));
+  if (n_keys && !keys) return fail(DG_E_INVAL, "dg_merkle_update: null keys");
+  TRY(set_device(e));
+  TRY(settle(e));
+  return tree_update(e, t, old_s, new_s, keys, n_keys, "dg_merkle_update");
+}
+
+int dg_merkle_diff(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
+                   const dg_store* sb, uint64_t* out_keys, uint64_t cap, uint64_t* n_out,
+                   uint64_t* n_total) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(a, "dg_merkle_diff a"));
+  TRY(check_merkle(b, "dg_merkle_diff b"));
+  TRY(same_tree_shape(a, b, "dg_merkle_diff"));
+  TRY(check_store(sa, "dg_merkle_diff sa"));
+  TRY(check_store(sb, "dg_merkle_diff sb"));
+  if (!n_out) return fail(DG_E_INVAL, "dg_merkle_diff: null n_out");
+  if (cap && !out_keys) return fail(DG_E_INVAL, "dg_merkle_diff: null out_keys");
+  TRY(set_device(e));
+  TRY(settle(e));
+  TRY(ensure_tmp(e, diff_scratch_words(a->depth, sa->n, sb->n) * sizeof(u64)));
+  TRY(ensure_diff_bsum(e, diff_groups(a->depth)));
+  HIP_TRY(enqueue_merkle_diff(e, a, sa, b, sb, out_keys, cap, e->d_counts));
+  TRY(read_counts(e));
+  const u64 total = e->h_counts[JC_ROWS];
+  if (total >= DIFF_MISMATCH) {
+    *n_out = 0;
+    if (n_total) *n_total = 0;
+    return fail(DG_E_INVAL, "dg_merkle_diff: a tree counts more rows than its store holds "
+                            "(the store is not the one the tree was built / updated against)");
+  }
+  *n_out = std::min<u64>(total, cap);
+  if (n_total) *n_total = total;
+  return DG_OK;
+}
+
+int dg_merkle_diff_async(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
+                         const dg_store* sb, uint64_t* out_keys, uint64_t cap, uint64_t* d_total) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(a, "dg_merkle_diff_async a"));
+  TRY(check_merkle(b, "dg_merkle_diff_async b"));
+  TRY(same_tree_shape(a, b, "dg_merkle_diff_async"));
+  TRY(check_store(sa, "dg_merkle_diff_async sa"));
+  TRY(check_store(sb, "dg_merkle_diff_async sb"));
+  if (!d_total) return fail(DG_E_INVAL, "dg_merkle_diff_async: null d_total");
+  if (cap && !out_keys) return fail(DG_E_INVAL, "dg_merkle_diff_async: null out_keys");
+  TRY(set_device(e));
+  TRY(settle(e));  // (a logged join that aborted is replayed before its output is read)
+  TRY(ensure_tmp(e, diff_scratch_words(a->depth, sa->n, sb->n) * sizeof(u64)));
+  TRY(ensure_diff_bsum(e, diff_groups(a->depth)));
+  HIP_TRY(enqueue_merkle_diff(e, a, sa, b, sb, out_keys, cap, d_total));
+  return DG_OK;
+}
+
+int dg_merkle_prepare(dg_engine* e, const dg_merkle* t, uint32_t levels, dg_merkle_cont* out) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(t, "dg_merkle_prepare"));
+  if (!out || levels < 1) return fail(DG_E_INVAL, "dg_merkle_prepare: bad arguments");
+  const u32 L = std::min<u32>(levels, t->depth);
+  const u64 n = 1ull << L;
+  out->level = L;
+  out->n = n;
+  out->n_buckets = 0;
+  if (out->cap < n || !out->pos || !out->hash)
+    return fail(DG_E_CAPACITY, "dg_merkle_prepare: %llu entries needed", (unsigned long long)n);
+  TRY(set_device(e));
+  TRY(settle(e));
+  HIP_TRY(launch_cont_prepare(merkle_of(t), L, out->pos, out->hash, e->stream));
+  return sync_words(e);
+}
+
+int dg_merkle_continue(dg_engine* e, const dg_merkle* t, const dg_store* s, const dg_merkle_cont* in,
+                       uint32_t levels, dg_merkle_cont* out, uint64_t* keys, uint64_t cap,
+                       uint64_t* n_keys, uint64_t* n_total, int* status) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(t, "dg_merkle_continue"));
+  TRY(check_store(s, "dg_merkle_continue"));
+  if (!in || !status || !n_keys || levels < 1 || (cap && !keys))
+    return fail(DG_E_INVAL, "dg_merkle_continue: bad arguments");
+  if (in->n && (!in->pos || !in->hash)) return fail(DG_E_INVAL, "dg_merkle_continue: null input");
+  *n_keys = 0;
+  if (n_total) *n_total = 0;
+  *status = 0;
+  TRY(set_device(e));
+  TRY(settle(e));
+  const u32 depth = t->depth;
+  const MerkleT m = merkle_of(t);
+  if (in->level == depth + 1) {  // leaf form: the keys
+    if (in->n_buckets && !in->bucket) return fail(DG_E_INVAL, "dg_merkle_continue: null buckets");
+    TRY(ensure_state(e, 2 * cont_tiles(in->n_buckets) + 2));
+    HIP_TRY(launch_leafdiff(m, rows_of(s), in->bucket, in->n_buckets, in->pos, in->hash, in->n, keys,
+                            cap, e->state.as<u64>(), e->d_counts, e->stream));
+    TRY(read_counts(e));
+    const u64 total = e->h_counts[JC_ROWS];
+    *n_keys = std::min<u64>(total, cap);
+    if (n_total) *n_total = total;
+    return DG_OK;
+  }
+  if (in->level > depth) return fail(DG_E_INVAL, "dg_merkle_continue: level %u > depth %u", in->level, depth);
+  if (!out) return fail(DG_E_INVAL, "dg_merkle_continue: null out");
+  const u32 L = in->level;
+  TRY(ensure_state(e, 2 * cont_tiles(in->n) + 2));
+  TRY(ensure_tmp(e, std::max<u64>(in->n, 1) * sizeof(u64)));
+  u64* dpos = e->tmp.as<u64>();
+  HIP_TRY(launch_cont_compare(m, L, in->pos, in->hash, in->n, e->state.as<u64>(), dpos, e->d_counts, e->stream));
+  TRY(read_counts(e));
+  const u64 nd = e->h_counts[JC_ROWS];
+  if (nd == 0) return DG_OK;  // {:ok, []}
+  if (L < depth) {
+    const u32 k = std::min<u32>(levels, depth - L);
+    const u64 need = nd << k;
+    out->level = L + k;
+    out->n = need;
+    out->n_buckets = 0;
+    if (out->cap < need || !out->pos || !out->hash)
+      return fail(DG_E_CAPACITY, "dg_merkle_continue: %llu entries needed", (unsigned long long)need);
+    HIP_TRY(launch_cont_expand(m, L, k, dpos, nd, out->pos, out->hash, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *status = 1;
+    return DG_OK;
+  }
+  // the differing buckets -> leaf form
+  out->level = depth + 1;
+  out->n_buckets = nd;
+  if (out->cap_buckets < nd || !out->bucket)
+    return fail(DG_E_CAPACITY, "dg_merkle_continue: %llu buckets needed", (unsigned long long)nd);
+  HIP_TRY(hipMemcpyAsync(out->bucket, dpos, nd * sizeof(u64), hipMemcpyDeviceToDevice, e->stream));
+  TRY(ensure_state(e, 2 * cont_tiles(nd) + 2));
+  HIP_TRY(launch_leaves_count(m, rows_of(s), out->bucket, nd, e->state.as<u64>(), e->d_counts, e->stream));
+  TRY(read_counts(e));
+  const u64 np = e->h_counts[JC_ROWS];
+  out->n = np;
+  if (out->cap < np || (np && (!out->pos || !out->hash)))
+    return fail(DG_E_CAPACITY, "dg_merkle_continue: %llu leaf pairs needed", (unsigned long long)np);
+  HIP_TRY(launch_leaves_write(m, rows_of(s), out->bucket, nd, e->state.as<u64>(), out->pos, out->hash, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  *status = 1;
+  return DG_OK;
+}
+
+int dg_merkle_continue_home(dg_engine* e, const dg_merkle* t, const dg_store* s, const dg_merkle_cont* in,
+                            uint32_t levels, uint64_t max, dg_merkle_cont* out, uint64_t* keys, uint64_t cap,
+                            uint64_t* n_keys, uint64_t* n_total, int* status) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(t, "dg_merkle_continue_home"));
+  TRY(check_store(s, "dg_merkle_continue_home"));
+  if (!in || !status || !n_keys || levels < 1 || (cap && !keys))
+    return fail(DG_E_INVAL, "dg_merkle_continue_home: bad arguments");
+  if (in->n && (!in->pos || !in->hash)) return fail(DG_E_INVAL, "dg_merkle_continue_home: null input");
+  const u32 depth = t->depth;
+  const bool leaf = in->level == depth + 1;
+  if (in->level > depth + 1) return fail(DG_E_INVAL, "dg_merkle_continue_home: level %u > depth %u", in->level, depth);
+  if (leaf && in->n_buckets && !in->bucket) return fail(DG_E_INVAL, "dg_merkle_continue_home: null buckets");
+  *n_keys = 0;
+  if (n_total) *n_total = 0;
+  *status = DG_CONT_DECLINED;
+  if (in->n > CS_IN || (leaf && in->n_buckets > CS_B)) return DG_OK;  // the general path
+  *status = 0;
+  if (leaf ? in->n_buckets == 0 : in->n == 0) return DG_OK;  // {:ok, []}
+  if (!leaf && !out) return fail(DG_E_INVAL, "dg_merkle_continue_home: null out");
+  TRY(set_device(e));
+  TRY(settle(e));
+  ContSmallArgs a{};
+  a.t = merkle_of(t);
+  a.s = rows_of(s);
+  a.level = in->level;
+  a.levels = levels;
+  a.max = max;
+  a.ipos = in->pos;
+  a.ihash = in->hash;
+  a.ibucket = leaf ? in->bucket : nullptr;
+  a.n = in->n;
+  a.nb = leaf ? in->n_buckets : 0;
+  if (out) {
+    a.opos = out->pos;
+    a.ohash = out->hash;
+    a.obucket = out->bucket;
+    a.ocap = out->pos && out->hash ? out->cap : 0;
+    a.ocap_b = out->bucket ? out->cap_buckets : 0;
+  }
+  a.keys = keys;
+  a.kcap = cap;
+  a.home = e->d_pub + CONT_HOME;
+  a.d_counts = e->d_counts;
+  a.h_pub = e->d_pub;
+  a.seq = ++e->pub_seq;
+  HIP_TRY(launch_cont_small(a, e->stream));
+  TRY(wait_published(e, a.seq));
+  u64 h[CS_HDR];
+  memcpy(h, (const void*)(e->h_pub + CONT_HOME), sizeof h);
+  if (h[0] == CS_BAD)
+    return fail(DG_E_INVAL, "dg_merkle_continue_home: a position or bucket outside the tree");
+  if (h[0] == CS_CAP) {
+    out->level = (u32)h[3];
+    out->n = h[4];
+    out->n_buckets = h[5];
+    *status = 0;
+    return fail(DG_E_CAPACITY, "dg_merkle_continue_home: %llu entries / %llu buckets needed",
+                (unsigned long long)h[4], (unsigned long long)h[5]);
+  }
+  if (h[0] == CS_OK) {
+    *n_keys = std::min<u64>(h[1], cap);
+    if (n_total) *n_total = h[1];
+    return DG_OK;
+  }
+  out->level = (u32)h[3];
+  out->n = h[1];
+  out->n_buckets = h[0] == CS_LEAF ? h[2] : 0;
+  *status = 1;
+  return DG_OK;
+}
+
+int dg_merkle_truncate(dg_engine* e, const dg_merkle* t, dg_merkle_cont* cont, uint64_t max) {
+  if (!e || !cont) return fail(DG_E_INVAL, "dg_merkle_truncate: null argument");
+  TRY(check_merkle(t, "dg_merkle_truncate"));
+  if (cont->n_buckets == 0 || cont->bucket == nullptr) {  // node form (or an empty leaf form)
+    cont->n = std::min<u64>(cont->n, max);
+    return DG_OK;
+  }
+  if (cont->n_buckets <= max) return DG_OK;
+  // leaf form: the pairs of the first `max` buckets are those whose key sorts before
+  // the first pair of bucket[max]; pairs carry keys, buckets carry bucket numbers, so
+  // count the pairs of the dropped buckets by their bucket's first pair
+  TRY(set_device(e));
+  TRY(settle(e));
+  TRY(ensure_state(e, 2));
+  HIP_TRY(launch_pairs_before_bucket(merkle_of(t), cont->pos, cont->n, cont->bucket + max,
+                                     e->d_counts, e->stream));
+  TRY(read_counts(e));
+  cont->n = e->h_counts[JC_ROWS];
+  cont->n_buckets = max;
+  return DG_OK;
+}
+
+uint64_t dg_merkle_chunks(uint32_t depth) { return merkle_chunks(depth); }
+
+int dg_merkle_fold_roots(const uint64_t* roots, uint32_t shard_bits, uint64_t* root) {
+  if (!roots || !root || shard_bits > 16) return fail(DG_E_INVAL, "dg_merkle_fold_roots: bad arguments");
+  std::vector<u64> lvl(roots, roots + (1ull << shard_bits));
+  while (lvl.size() > 1) {
+    std::vector<u64> up(lvl.size() / 2);
+    for (size_t i = 0; i < up.size(); i++) up[i] = node_hash(lvl[2 * i], lvl[2 * i + 1]);
+    lvl.swap(up);
+  }
+  *root = lvl[0];
+  return DG_OK;
+}
+
+}  // extern "C"

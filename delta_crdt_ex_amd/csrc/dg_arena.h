@@ -1,0 +1,274 @@
+// dg_arena.h — the scratch layouts of the C-ABI layer, each written once.  Host only, no
+// HIP: a layout function takes an Arena and the sizes it needs and returns the pointers.
+// The caller runs it on a measuring arena (null base) for the byte count, grows the buffer,
+// and runs it again on the buffer: the size and the pointers come from the same lines
+// (tests/arena_layouts.cc checks every layout against its offsets and under ASan).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
+
+#include "../../include/deltagpu.h"
+
+namespace dg {
+
+constexpr size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// A bump allocator over a buffer that need not exist yet.  Regions start where the one
+// before ended; `align` rounds a region's SIZE (256 B: every region of a 256-B aligned
+// buffer then starts 256-B aligned, and a column of an odd row count has padding behind
+// it, which the 16-byte pair stores of the splice and the one-wait join rely on).
+struct Arena {
+  char* base;
+  size_t off = 0;
+  explicit Arena(void* b = nullptr) : base((char*)b) {}
+  template <class T>
+  T* take(size_t count, size_t align = 256) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += round_up(count * sizeof(T), align);
+    return p;
+  }
+  void align_to(size_t a) { off = round_up(off, a); }
+  // A store of `rows` rows (n = 0); the column order is part of the layout.
+  dg_store store(uint64_t rows) {
+    dg_store s{};
+    s.key = take<uint64_t>(rows);
+    s.val = take<uint64_t>(rows);
+    s.ts = take<int64_t>(rows);
+    s.cnt = take<uint64_t>(rows);
+    s.node = take<uint32_t>(rows);
+    s.cap = rows;
+    return s;
+  }
+  // A context of `cap` entries (n = 0, a version vector until a join says otherwise).
+  dg_context context(uint64_t cap) {
+    dg_context c{};
+    c.cnt = take<uint64_t>(cap);
+    c.node = take<uint32_t>(cap);
+    c.cap = cap;
+    c.kind = DG_CTX_VV;
+    return c;
+  }
+  // the buffer to allocate: never empty, so that no carved pointer is null
+  size_t bytes() const { return off ? round_up(off, 256) : 256; }
+};
+
+// join2_enqueue (engine tmp): the context union's scratch | the two-pass join's counts
+// (pass_bytes 0: single pass) | the change events (chg_bytes 0: none, chg null)
+struct JoinScratch {
+  void *ctx, *pass, *chg;
+};
+inline JoinScratch join_layout(Arena& a, size_t ctx_bytes, size_t pass_bytes, size_t chg_bytes) {
+  JoinScratch s;
+  s.ctx = a.take<char>(ctx_bytes);
+  s.pass = a.take<char>(pass_bytes);
+  s.chg = chg_bytes ? a.take<char>(chg_bytes) : nullptr;
+  return s;
+}
+
+// The per-key index of a splice: five arrays of nk + 1 entries
+struct KeyIndex {
+  uint64_t *a_lo, *a_off, *end;
+  int64_t *shift, *gap;
+};
+inline KeyIndex key_index(Arena& a, uint64_t nk) {
+  KeyIndex x;
+  x.a_lo = a.take<uint64_t>(nk + 1);
+  x.a_off = a.take<uint64_t>(nk + 1);
+  x.end = a.take<uint64_t>(nk + 1);
+  x.shift = a.take<int64_t>(nk + 1);
+  x.gap = a.take<int64_t>(nk + 1);
+  return x;
+}
+
+// The splice (engine spl): the state's rows of the keyset | the edit | the per-key index |
+// the per-tile entry ranges | the join's union context
+struct SpliceScratch {
+  dg_store ak, ed;
+  KeyIndex idx;
+  uint64_t* tile_u0;
+  dg_context uctx;
+};
+inline SpliceScratch splice_layout(Arena& a, uint64_t cap_k, uint64_t cap_e, uint64_t nk, uint64_t a_tiles,
+                                   uint64_t uctx_cap) {
+  SpliceScratch s;
+  s.ak = a.store(cap_k);
+  s.ed = a.store(cap_e);
+  s.idx = key_index(a, nk);
+  s.tile_u0 = a.take<uint64_t>(a_tiles + 1);
+  s.uctx = a.context(uctx_cap);
+  return s;
+}
+
+// dg_join_delta's one-wait path (engine kdb): seven per-key figures | shift (nk + 1) | the
+// count workgroups' figures | the per-tile entry ranges | the union context and its
+// scratch | with diffs, the per-key winners (last, and only then)
+struct KdScratch {
+  uint64_t *a_lo, *d_lo, *runs, *amask, *dmask, *dh, *end;
+  int64_t* shift;
+  uint64_t *part, *tile_u0;
+  dg_context uctx;
+  void* cu_tmp;
+  uint64_t *dv_old, *dv_new;
+};
+inline KdScratch kd_layout(Arena& a, uint64_t nk, uint64_t part_words, uint64_t a_tiles, uint64_t uctx_cap,
+                           size_t cu_bytes, bool diffs) {
+  KdScratch s;
+  for (uint64_t** q : {&s.a_lo, &s.d_lo, &s.runs, &s.amask, &s.dmask, &s.dh, &s.end}) *q = a.take<uint64_t>(nk);
+  s.shift = a.take<int64_t>(nk + 1);
+  s.part = a.take<uint64_t>(part_words);
+  s.tile_u0 = a.take<uint64_t>(a_tiles + 2);
+  s.uctx = a.context(uctx_cap);
+  s.cu_tmp = a.take<char>(cu_bytes);
+  s.dv_old = diffs ? a.take<uint64_t>(nk) : nullptr;
+  s.dv_new = diffs ? a.take<uint64_t>(nk) : nullptr;
+  return s;
+}
+
+// dg_join_delta_home (engine sml): the edit | the per-key index (and a sixth, unused array
+// that keeps the offsets behind it) | the per-tile entry ranges | the moved word | the
+// result block
+struct HomeScratch {
+  dg_store ed;
+  KeyIndex idx;
+  uint64_t* tile_u0;
+  uint32_t* moved;
+  uint64_t* res;
+};
+inline HomeScratch home_layout(Arena& a, uint64_t edit_rows, uint64_t nk, uint64_t a_tiles,
+                               uint64_t result_words) {
+  HomeScratch s;
+  s.ed = a.store(edit_rows);
+  s.idx = key_index(a, nk);
+  a.take<uint64_t>(nk + 1);
+  s.tile_u0 = a.take<uint64_t>(a_tiles + 2);
+  s.moved = a.take<uint32_t>(1);
+  s.res = a.take<uint64_t>(result_words);
+  return s;
+}
+
+// The tree update's scratch: the hand-off words | the dirty flags (u32, padded to even so
+// that cdelta is 8-byte aligned) | the per-chunk row-count changes.  dg_merkle_update has
+// all three in engine tmp (hand and flags the same arena); the one-wait path keeps the
+// flags and changes in a buffer of their own that stays zero between calls.  zero_words:
+// the u32 words from `dirty` on, which one launch zeroes.
+struct TreeScratch {
+  uint64_t* hand;
+  uint32_t* dirty;
+  int64_t* cdelta;
+  uint64_t zero_words;
+};
+inline TreeScratch tree_layout(Arena& hand, Arena& flags, uint64_t ctr_words, uint64_t chunks) {
+  const uint64_t cpad = (chunks + 1) & ~1ull;
+  TreeScratch s;
+  s.hand = (uint64_t*)hand.take<uint32_t>(ctr_words, 8);
+  s.dirty = flags.take<uint32_t>(cpad, 8);
+  s.cdelta = flags.take<int64_t>(chunks, 8);
+  s.zero_words = cpad + 2 * chunks;
+  return s;
+}
+
+// A fold's two intermediate states (engine fold).  The one PACKED layout: columns are not
+// padded, so a column's alignment -- and with it whether a stepwise fold's intermediate
+// passes pair_aligned and splices -- follows the parity of `rows`.  Each half ends with 1 KiB
+// of padding, rounded up to 256 B.
+struct FoldScratch {
+  dg_store st[2];
+  dg_context cx[2];
+};
+inline FoldScratch fold_layout(Arena& a, uint64_t rows, uint64_t ctx) {
+  FoldScratch s;
+  for (int w = 0; w < 2; w++) {
+    dg_store& st = s.st[w] = dg_store{};
+    dg_context& cx = s.cx[w] = dg_context{};
+    st.key = a.take<uint64_t>(rows, 8);
+    st.val = a.take<uint64_t>(rows, 8);
+    st.ts = a.take<int64_t>(rows, 8);
+    st.cnt = a.take<uint64_t>(rows, 8);
+    cx.cnt = a.take<uint64_t>(ctx, 8);
+    st.node = a.take<uint32_t>(rows, 4);
+    cx.node = a.take<uint32_t>(ctx, 4);
+    a.take<char>(1024, 1);
+    a.align_to(256);
+    st.cap = rows;
+    cx.cap = ctx;
+    cx.kind = DG_CTX_VV;
+  }
+  return s;
+}
+
+// The one-pass fold (kfold_pass).  Staged in pinned memory and copied to the head of engine
+// tmp: the k run descriptors | the dots' offsets (k + 1).  Behind them on the device: the
+// state's bucket starts (T + 1) | the deltas' (T + 1 per run and kind) | the two VV tables
+// (k * nodes each) | the flag | the dot set (dset_n 0: no DOTS delta, dset null).
+struct KfoldStaged {
+  void* runs;
+  uint64_t* cflat;
+};
+inline KfoldStaged kfold_staged_layout(Arena& a, uint64_t k, size_t run_bytes) {
+  KfoldStaged s;
+  s.runs = a.take<char>(k * run_bytes);
+  s.cflat = a.take<uint64_t>(k + 1);
+  return s;
+}
+struct KfoldScratch {
+  KfoldStaged staged;
+  size_t staged_bytes;  // what the host copies in
+  uint64_t* sstart;
+  uint32_t* dstart;
+  uint64_t *tabC, *tabP;
+  uint32_t* flag;
+  size_t zero_bytes;  // from sstart through the flag: zeroed per attempt
+  uint64_t* dset;
+};
+inline KfoldScratch kfold_layout(Arena& a, uint64_t k, size_t run_bytes, uint64_t T, uint64_t nodes,
+                                 uint64_t dset_n) {
+  KfoldScratch s;
+  s.staged = kfold_staged_layout(a, k, run_bytes);
+  s.staged_bytes = a.off;
+  s.sstart = a.take<uint64_t>(T + 1);
+  s.dstart = a.take<uint32_t>((T + 1) * 2 * k);
+  s.tabC = a.take<uint64_t>(k * nodes);
+  s.tabP = a.take<uint64_t>(k * nodes);
+  s.flag = a.take<uint32_t>(1);
+  s.zero_bytes = a.off - s.staged_bytes;
+  s.dset = dset_n ? a.take<uint64_t>(dset_n) : nullptr;
+  return s;
+}
+
+// dg_mutate_batch (engine tmp): the delta's dots (node | cnt) | their sort's second pair |
+// the sort's scratch
+struct MutateScratch {
+  uint32_t* dnode;
+  uint64_t* dcnt;
+  uint32_t* tnode;
+  uint64_t* tcnt;
+  void* sort_tmp;
+};
+inline MutateScratch mutate_layout(Arena& a, uint64_t n_dots, size_t sort_bytes) {
+  MutateScratch s;
+  s.dnode = a.take<uint32_t>(n_dots);
+  s.dcnt = a.take<uint64_t>(n_dots);
+  s.tnode = a.take<uint32_t>(n_dots);
+  s.tcnt = a.take<uint64_t>(n_dots);
+  s.sort_tmp = a.take<char>(sort_bytes);
+  return s;
+}
+
+// dg_mark_ids (engine tmp): the column descriptors (n_stores + 1, staged in pinned memory
+// first) | the bitmap | the id samples
+struct MarkScratch {
+  void* segs;
+  uint32_t* bitmap;
+  uint64_t* samples;
+};
+inline MarkScratch mark_layout(Arena& a, uint64_t n_stores, size_t seg_bytes, uint64_t bitmap_words,
+                               uint64_t samples) {
+  MarkScratch s;
+  s.segs = a.take<char>((n_stores + 1) * seg_bytes);
+  s.bitmap = a.take<uint32_t>(bitmap_words);
+  s.samples = a.take<uint64_t>(samples);
+  return s;
+}
+
+}  // namespace dg

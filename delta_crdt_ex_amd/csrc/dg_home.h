@@ -4,7 +4,7 @@
 // whichever kernel ends the call (the small join itself, or the tail kernel's last
 // workgroup when it copies moved rows) then copies the engine's count block into the
 // mapped publish words and, after a system fence, stores the sequence number the host
-// polls (api.hip wait_published).  Called by every thread of the workgroup.
+// polls (api_engine.hip wait_published).  Called by every thread of the workgroup.
 #pragma once
 #include "dg_launch.h"
 

@@ -1,5 +1,5 @@
 // dg_launch.h — host-side launchers exported by each kernel translation unit to the
-// C-ABI layer (api.hip).  Plain structs only; no torch types anywhere in libdeltagpu.
+// C-ABI layer (api_*.hip).  Plain structs only; no torch types anywhere in libdeltagpu.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

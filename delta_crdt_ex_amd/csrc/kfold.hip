@@ -33,7 +33,7 @@
 //                       survivors of each key by tuple, resolves the bucket's output
 //                       offset by decoupled look-back and writes the rows.
 // A bucket that overflows its LDS capacity (keys far from uniform) sets a flag and the
-// caller re-runs the fold step by step (api.hip); nothing falls back to the CPU.
+// caller re-runs the fold step by step (api_fold.hip); nothing falls back to the CPU.
 #include "dg_launch.h"
 
 namespace dg {

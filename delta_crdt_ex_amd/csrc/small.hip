@@ -2,7 +2,7 @@
 //
 // CausalCrdt joins every local mutation and every small sync delta into the replica
 // (reference causal_crdt.ex:337-342,383-394; aw_lww_map.ex:153-209).  The general
-// dg_join_delta (api.hip) takes the keyset's rows out, joins them on the join kernels,
+// dg_join_delta (api_join_delta.hip) takes the keyset's rows out, joins them on the join kernels,
 // splices, updates the tree and gathers the changed rows: four steps, each sized by the
 // counts of the one before, so four host waits -- ~80 us for a one-key mutation of which
 // the device work is a few.  Here ONE workgroup does the whole join of a delta of at most
@@ -280,7 +280,7 @@ __device__ u64 g_sm_stamps[16];
   do {            \
   } while (0)
 #endif
-constexpr int TMAXD = 28;  // the deepest tree (api.hip check_merkle)
+constexpr int TMAXD = 28;  // the deepest tree (api_engine.hip check_merkle)
 
 // the sibling of bucket b's ancestor l levels up (node 0 past the root): every lane
 // loads every level unconditionally, so all the loads are in flight together (a load

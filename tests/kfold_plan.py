@@ -1,5 +1,5 @@
 """A CPU model of the one-pass fold's bucket plan (csrc/kfold.hip, kfold_pass in
-csrc/api.hip), and inputs built to reach its seams (helper module: no tests).
+csrc/api_fold.hip), and inputs built to reach its seams (helper module: no tests).
 
 The fold cuts the key space into T equal buckets sized by means, stages every bucket in
 fixed LDS arrays, flags KF_OVERFLOW when one does not fit and retries once with 8 T.  From

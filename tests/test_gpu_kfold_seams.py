@@ -1,4 +1,4 @@
-"""dg_apply_deltas' one-pass fold (csrc/kfold.hip, kfold_pass in csrc/api.hip) at its
+"""dg_apply_deltas' one-pass fold (csrc/kfold.hip, kfold_pass in csrc/api_fold.hip) at its
 bucket capacities, on skewed keys and at its other seams, bit-exact against the C oracle's
 delta-by-delta fold (which tests/test_kfold_plan.py pins to the term oracle on these shapes).
 

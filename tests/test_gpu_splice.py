@@ -1,4 +1,4 @@
-"""The sparse keyed join as a splice (csrc/splice.hip; api.hip splice_join): a sync delta
+"""The sparse keyed join as a splice (csrc/splice.hip; api_join.hip splice_join): a sync delta
 Map.take(B, K) joined into a large state with its keyset K (causal_crdt.ex:383-384),
 bit-exact against the C oracle's keyed join and CausalCrdt's changed keys, and equal to
 the full-merge join (DG_SPLICE=0) -- including the inputs on which the splice hands over

@@ -47,7 +47,7 @@ def test_constants_match_the_header():
     # the two overflow predicates and the retry factor, as the model restates them
     assert "nS > (u32)CS || nD > (u32)CD || nU > (u32)CUL || nU - nD > (u32)(CUL - CD)" in k
     assert "nD + n_keep > (u32)CU" in k
-    assert "T0 << (3 * attempt)" in open(os.path.join(CSRC, "api.hip")).read()
+    assert "T0 << (3 * attempt)" in open(os.path.join(CSRC, "api_fold.hip")).read()
     assert (P.CS, P.CD, P.CU, P.CUL, P.KB) == (1024, 512, 1024, 1536, 1024)
 
 
