@@ -350,7 +350,7 @@ static int join_delta_core(dg_engine* e, dg_store* state, dg_context* state_ctx,
 
 // dg_join_delta_home: the fused small-delta join (small.hip) with ONE host wait.  States
 // of up to SMALL_COPY_TILES splice tiles get the moved-rows copy in the tail launch behind
-// the join (merkle.hip small_tail_kernel: with the tree's upsweep and the publish),
+// the join (small.hip small_tail_kernel: the copy, then the publish),
 // guarded by its `moved` word; a larger state whose rows moved copies after the wait.
 constexpr u64 SMALL_COPY_TILES = 64;
 static_assert(DIFF_MISMATCH == DG_DIFF_MISMATCH, "deltagpu.h and the diff kernels agree");

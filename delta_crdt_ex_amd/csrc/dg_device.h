@@ -197,6 +197,19 @@ __device__ __forceinline__ bool ctx_covers(const u32* node, const u64* cnt, u64 
   return lo < n && node[lo] == dn && cnt[lo] == dc;
 }
 
+// First index of k[lo, hi) (ascending) that is >= x (hi if none): a plain binary search.
+// `k` may point at LDS or global memory.
+__device__ __forceinline__ u64 lower_bound(const u64* k, u64 lo, u64 hi, u64 x) {
+  while (lo < hi) {
+    const u64 mid = (lo + hi) >> 1;
+    if (k[mid] < x)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
 // First index of keys[0, n) (ascending) that is >= x, by ONE wave: a 64-ary search
 // (every step probes 64 positions, one dependent load round: 12.5M rows in 4 rounds
 // instead of a 24-load binary-search chain).  Every lane returns the same value.

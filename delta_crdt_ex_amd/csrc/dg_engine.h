@@ -122,16 +122,7 @@ enum JoinCount {    // the join kernels, and the splice around them
   SC_BAD = 4,       // delta keys outside the keyset (splice_check_kernel)
   SC_MOVED = 5,     // u32: the edit moves rows (splice_index_kernel)
 };
-enum KdCount {      // dg_join_delta's one-wait path: kd_finish's scan (kdelta.hip), but KC_CTX
-  KC_EDIT = 0,      // the keyset's joined rows
-  KC_CTX = 1,       // the union context's entries (ctx_union_block)
-  KC_CHANGED = 2,   // changed keys
-  KC_ROWS = 3,      // their rows
-  KC_GUARD = 4,     // KD_BAD | KD_BIG | KD_CAP: nothing was written
-  KC_MOVED = 5,     // rows moved: the state is in `spare`
-  KC_TAKEN = 6,     // the state's rows of the keyset
-  KC_DKEYS = 7,     // the change in distinct keys
-};
+// (dg_join_delta's one-wait path: enum KdCount, dg_launch.h -- its kernels use the names too)
 enum HomeWord {     // dg_join_delta_home's result header home[0..8) (small.hip)
   HW_FLAGS = 0,     // SMALL_FALLBACK | MERKLE_INPUT_ERR bits
   HW_CTX = 3,       // the union context's entries
@@ -141,7 +132,7 @@ enum HomeWord {     // dg_join_delta_home's result header home[0..8) (small.hip)
   HW_DKEYS = 7,     // the change in distinct keys
 };
 constexpr int TU_SHARDS = 8;  // the tree update: d_counts[0..8) are shards of the change in
-                              // distinct keys (merkle.hip), summed by the host
+                              // distinct keys (merkle_build.hip), summed by the host
 enum MutateCount {  // mutate_count_kernel's last tile
   MC_KEYS = 0,      // touched keys
   MC_ROWS = 1,      // delta rows

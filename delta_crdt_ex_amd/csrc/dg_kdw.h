@@ -1,5 +1,5 @@
 // dg_kdw.h — the write step of dg_join_delta's one-wait path (kdelta.hip), as a block
-// body: merkle.hip's kd_finish_kernel runs it in the same launch as the tree's chunk
+// body: merkle_build.hip's kd_finish_kernel runs it in the same launch as the tree's chunk
 // re-reduction (the two read only what kd_count_kernel wrote, so they overlap instead of
 // running back to back).
 //
@@ -25,12 +25,12 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
   const u64 u = blk * NT + tid;
   const u64 tile = u / KD_BLOCK;
-  const u64 guard = p.d_counts[4];
+  const u64 guard = p.d_counts[KC_GUARD];
   const bool tree_bad = p.err && (*p.err & MERKLE_INPUT_ERR);
   if (guard) return;  // (uniform) nothing is written: the caller falls back or reports
-  const bool moved = p.d_counts[5] != 0;
+  const bool moved = p.d_counts[KC_MOVED] != 0;
   if (blk == 0 && !tree_bad) {   // the union context into the state's (Dots.union, :155)
-    const u64 nc = p.d_counts[1];  // (and the caller's copy, when it fits)
+    const u64 nc = p.d_counts[KC_CTX];  // (and the caller's copy, when it fits)
     const bool co = p.co_node && nc <= p.co_cap;
     for (u64 i = tid; i < nc && i < p.ca_cap; i += NT) {
       const u32 n = p.uc_node[i];
@@ -102,7 +102,7 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
   const u64 k = p.keys[u];
   const u64 a_lo = p.a_lo[u], d_lo = p.d_lo[u], am = p.amask[u], dm = p.dmask[u];
   const u64 a_off = pre[0], e_off = pre[1], c_off = pre[2], r_off = pre[3];
-  const u64 n_e = p.d_counts[0], n_ak = p.d_counts[6];
+  const u64 n_e = p.d_counts[KC_EDIT], n_ak = p.d_counts[KC_TAKEN];
   // the splice index (splice.hip): where this key's rows go and where the untouched rows
   // before it move
   const i64 gap = (i64)a_lo - (i64)a_off;

@@ -302,7 +302,8 @@ hipError_t launch_mark_ids(const MarkSeg* segs, u64 n_segs, u64 n_tiles, u64 til
                            const u64* ids, u64 n_ids, u32* bitmap, u64* samples, uint8_t* used, u64* d_counts,
                            u32* bad, hipStream_t st);
 
-// ---- merkle.hip (see the file header)
+// ---- the Merkle tree (dg_tree.h describes it): merkle_build.hip (build, update, kd_finish),
+//      merkle_diff.hip (the whole-tree diff), merkle_cont.hip (the partial diff)
 // term hashes of a tree's rows (dg_term_hashes; on = 0: the ids themselves)
 struct TermH {
   const u64* nh;   // node_hash[node id]
@@ -355,10 +356,23 @@ constexpr int KD_BLOCK = 256;  // keys per workgroup
 constexpr u32 KD_RUN = 64;     // rows per key and side the per-key join takes (more: KD_BIG)
 constexpr int KD_NV = 7;       // per-workgroup figures: rows, kept rows, changed keys, their rows,
                                // delta rows, distinct-key change, flags
-// guard bits (d_counts[4]): the delta has a row outside the keyset (the full join applies);
-// a key run over KD_RUN rows (the splice applies); more changed keys than `cap`
+// guard bits (d_counts[KC_GUARD]): the delta has a row outside the keyset (the full join
+// applies); a key run over KD_RUN rows (the splice applies); more changed keys than `cap`
 constexpr u64 KD_BAD = 1, KD_BIG = 2, KD_CAP = 4;
 constexpr u64 KD_MOVED = 8;    // (flags only) a key's row count changed
+// the count block d_counts[0..8) of this path (and its host mirror): written by the count
+// kernel's last workgroup (kdelta.hip), but KC_CTX; read by the write (dg_kdw.h),
+// kd_finish_kernel and the host (api_join_delta.hip)
+enum KdCount {
+  KC_EDIT = 0,      // the keyset's joined rows
+  KC_CTX = 1,       // the union context's entries (ctx_union_block)
+  KC_CHANGED = 2,   // changed keys
+  KC_ROWS = 3,      // their rows
+  KC_GUARD = 4,     // KD_BAD | KD_BIG | KD_CAP: nothing was written
+  KC_MOVED = 5,     // rows moved: the state is in `spare`
+  KC_TAKEN = 6,     // the state's rows of the keyset
+  KC_DKEYS = 7,     // the change in distinct keys
+};
 struct KdArgs {
   Rows a;              // the state (read)
   RowsOut aw;          // the same columns (the in-place write)
@@ -410,7 +424,7 @@ struct KdArgs {
 constexpr u32 KD_DIFF_OLD = 1, KD_DIFF_NEW = 2;  // (deltagpu.h DG_DIFF_OLD / DG_DIFF_NEW)
 // kd_count_kernel / kd_count_diffs_kernel (its last workgroup scans)
 hipError_t launch_kd_join(const KdArgs& p, hipStream_t st);
-// kd_finish_kernel (merkle.hip): the write (dg_kdw.h) and, with a tree, its dirty chunks' re-reduction in one launch
+// kd_finish_kernel (merkle_build.hip): the write (dg_kdw.h) and, with a tree, its dirty chunks' re-reduction in one launch
 hipError_t launch_kd_finish(const KdArgs& p, const u32* dirty, u32* arrive, u64* hand, const i64* cdelta,
                             hipStream_t st);
 
@@ -502,7 +516,7 @@ constexpr u64 DIFF_MISMATCH = 1ull << 44;
 hipError_t launch_merkle_diff(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb,
                               u64* out_keys, u64 cap, u64* scratch, u64* bsum, u64* bsum_zero, u64 nzero,
                               u64* d_count, hipStream_t st);
-// dg_merkle_continue_home's one-workgroup hop (merkle.hip cont_small_kernel): limits,
+// dg_merkle_continue_home's one-workgroup hop (merkle_cont.hip cont_small_kernel): limits,
 // result kinds (home[0]) and arguments
 constexpr u32 CS_IN = 4096, CS_B = 512;  // entries / pairs in, buckets in (leaf form)
 constexpr u64 CS_OK = 0, CS_NODE = 1, CS_LEAF = 2, CS_CAP = 3, CS_BAD = 4;

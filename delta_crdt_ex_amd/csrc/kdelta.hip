@@ -22,7 +22,7 @@
 //                     launch computes the context union (Dots.union/2).
 //                     kd_count_diffs_kernel (dg_join_delta_diffs) is the same walk that also
 //                     keeps read/1's winner of the key's rows before and after the join.
-//   kd_finish_kernel  (merkle.hip + dg_kdw.h, one launch) one thread per key: its new rows --
+//   kd_finish_kernel  (merkle_build.hip + dg_kdw.h, one launch) one thread per key: its new rows --
 //                     in place when no key's row count changed, else straight to their
 //                     final places in the spare store -- the changed keys and their rows
 //                     (device or page-locked host memory), the splice index of the rows
@@ -51,10 +51,6 @@ constexpr int KDB = KD_BLOCK;  // keys per workgroup, one per thread
 constexpr u32 KVT = 1024;      // VV tables in LDS cover node ids < KVT
 static_assert(KD_RUN <= 64, "a key's kept rows are a 64-bit mask per side");
 
-__device__ __forceinline__ u64 rhash(const MerkleT& t, const Row& r) {
-  return row_hash(r.key, th_val(t.th, r.val), r.ts, th_node(t.th, r.node), r.cnt);
-}
-
 // Map.get(vv, node, 0) >= cnt through the LDS table (node ids < KVT), else a search
 __device__ __forceinline__ bool vv_covers(const u64* tab, const Ctx& c, u32 n, u64 cnt) {
   if (n < KVT) return tab[n] >= cnt;
@@ -82,36 +78,19 @@ __device__ __forceinline__ void key_run(const u64* key, u64 n, u64 k, u64& lo, u
   run = (u32)(e - lo);
 }
 
-// agent-scope stores and loads for the hand-off to the last workgroup (written through to
-// the point of coherence: the workgroups run on all eight XCDs)
-__device__ __forceinline__ void st_ag(u64* p, u64 v) {
-  __hip_atomic_store((__attribute__((address_space(1))) u64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 ld_ag(const u64* p) {
-  return __hip_atomic_load((__attribute__((address_space(1))) u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // MerkleMap.put/delete of the changed keys (the caller zeroed dirty and cdelta): key u's
 // leaf change d and row-count change dr.  The keys are ascending, so a wave's keys of one
-// bucket (and of one chunk) are adjacent lanes: segmented sums over the lanes leave ONE
-// atomic per bucket and per chunk.  merkle.hip's kd_tree_kernel applies the same with the
-// opposite sign to undo it.
-template <class T>
-__device__ __forceinline__ T seg_sum(T v, u64 seg, int lane) {
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const T y = __shfl_up(v, d, WAVE);
-    const u64 sy = __shfl_up(seg, d, WAVE);
-    if (lane >= d && sy == seg) v += y;  // (segments are contiguous runs of lanes)
-  }
-  return v;
-}
+// bucket (and of one chunk) are adjacent lanes: segmented sums over the lanes (seg_incl,
+// dg_tree.h) leave ONE atomic per bucket and per chunk.  merkle_build.hip's kd_tree_kernel
+// applies the same with the opposite sign to undo it.
 __device__ __forceinline__ void tree_put(const KdArgs& p, bool valid, u64 x, bool chg, u64 d, int dr) {
   const MerkleT& t = p.t;
   const int lane = threadIdx.x & (WAVE - 1);
   const u32 L1 = t.depth < MERKLE_UPL ? t.depth : MERKLE_UPL;
   bool bad = false, over = false;
   int act = 0;
+  // (bucket_of, dg_tree.h, spelled out: through the helper the compiler places one scalar
+  // instruction of the count kernels on the other side of a wait)
   const u64 b = valid ? (x << t.sb) >> (64 - t.depth) : ~0ull;
   if (valid && chg && (d != 0 || dr != 0)) {
     if (t.sb && (x >> (64 - t.sb)) != t.shard)
@@ -124,9 +103,9 @@ __device__ __forceinline__ void tree_put(const KdArgs& p, bool valid, u64 x, boo
     dr = 0;
   }
   const u64 c = b == ~0ull ? ~0ull : b >> L1;
-  const u64 sd = seg_sum<u64>(d, b, lane);
-  const int sr = seg_sum<int>(dr, b, lane), sa = seg_sum<int>(act, b, lane);
-  const int cr = seg_sum<int>(dr, c, lane), ca = seg_sum<int>(act, c, lane);
+  const u64 sd = seg_incl<u64>(d, b, lane);
+  const int sr = seg_incl<int>(dr, b, lane), sa = seg_incl<int>(act, b, lane);
+  const int cr = seg_incl<int>(dr, c, lane), ca = seg_incl<int>(act, c, lane);
   const u64 nb = __shfl_down(b, 1, WAVE), nc = __shfl_down(c, 1, WAVE);
   const bool last = lane == WAVE - 1;
   if (b != ~0ull && (last || nb != b) && sa) {  // the bucket's last lane: its node and row count
@@ -188,9 +167,9 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
   __shared__ u32 s_cw[KDB / WAVE + 1];
   if (blockIdx.x == 0) {
     // Dots.union(state context, delta context) (:155) into the union scratch and
-    // d_counts[1], by a workgroup of its own beside the keys' (it needs only the inputs; in
-    // the last workgroup's tail it added ~5 us to every call)
-    ctx_union_block<KDB>(make_cu(p.ca, p.cd, p.uc_node, p.uc_cnt, p.d_counts + 1, p.cu_tmp), s_cw);
+    // d_counts[KC_CTX], by a workgroup of its own beside the keys' (it needs only the inputs;
+    // in the last workgroup's tail it added ~5 us to every call)
+    ctx_union_block<KDB>(make_cu(p.ca, p.cd, p.uc_node, p.uc_cnt, p.d_counts + KC_CTX, p.cu_tmp), s_cw);
     return;
   }
   const u64 blk = blockIdx.x - 1;  // the keys' workgroups: 1 .. ntiles
@@ -289,7 +268,7 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
           ne++;
         } else {
           chg = true;
-          if (p.has_tree && DG_KD_EXP == 0) dh -= rhash(p.t, ra);
+          if (p.has_tree && DG_KD_EXP == 0) dh -= rh_row(p.t.th, ra);
         }
         if (c == 0 && ++j < nd) rb = load_row(p.d, d_lo + j);
         if (++i < na) ra = load_row(p.a, a_lo + i);
@@ -304,7 +283,7 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
           dm |= 1ull << j;
           ne++;
           chg = true;
-          if (p.has_tree && DG_KD_EXP == 0) dh += rhash(p.t, rb);
+          if (p.has_tree && DG_KD_EXP == 0) dh += rh_row(p.t.th, rb);
         }
         if (++j < nd) rb = load_row(p.d, d_lo + j);
       }
@@ -324,7 +303,7 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
     p.dh[u] = big ? 0ull : dh;
   }
   // the tree's put/delete right away (all or nothing: a guard or an input error found
-  // later makes the host undo it, merkle.hip kd_tree_kernel with the opposite sign)
+  // later makes the host undo it, merkle_build.hip kd_tree_kernel with the opposite sign)
   // (a key over KD_RUN keeps its bucket and chunk as its segment, with nothing to add, as in
   // the undo: were its lane left out, the keys of one bucket or chunk on either side of it
   // would be two runs of lanes, and the second run's sum takes the first's in again)
@@ -355,22 +334,21 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
     u64 s = 0;
 #pragma unroll
     for (int x = 0; x < KDB / WAVE; x++) s = tid < KD_NV - 1 ? s + red[tid][x] : (s | red[tid][x]);
-    st_ag(p.part + blk * KD_NV + tid, s);
+    st_sc1(p.part + blk * KD_NV + tid, s);
   }
   __syncthreads();
   if (tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmem();
     s_last = __hip_atomic_fetch_add(p.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p.ntiles - 1;
     if (s_last) __hip_atomic_store(p.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   KDSTAMP(0, 6);
   if (!s_last) return;
-  // ---- the last workgroup: the totals and the guard into the count block: [0] edit rows
-  // [2] changed keys [3] their rows [4] guard [5] moved [6] state rows of the keyset [7]
-  // distinct-key change (d_counts[1]: the context union's).  (The per-workgroup offsets are
-  // summed by the write's workgroups themselves, dg_kdw.h: a scan here was ~3 more round
-  // trips on the call's critical path.)
+  // ---- the last workgroup: the totals and the guard into the count block (KdCount,
+  // dg_launch.h; KC_CTX is the context union's).  (The per-workgroup offsets are summed by
+  // the write's workgroups themselves, dg_kdw.h: a scan here was ~3 more round trips on the
+  // call's critical path.)
   __shared__ u64 carry[KD_NV];
   {
     u64 x[KD_NV];
@@ -379,7 +357,7 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
     for (u64 t = tid; t < p.ntiles; t += KDB) {  // (every load of a round issued together)
       u64 y[KD_NV];
 #pragma unroll
-      for (int q = 0; q < KD_NV; q++) y[q] = ld_ag(p.part + t * KD_NV + q);
+      for (int q = 0; q < KD_NV; q++) y[q] = ld_sc1(p.part + t * KD_NV + q);
 #pragma unroll
       for (int q = 0; q < KD_NV; q++) x[q] = q < KD_NV - 1 ? x[q] + y[q] : (x[q] | y[q]);
     }
@@ -407,13 +385,13 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
     u64 g = carry[6] & KD_BIG;
     if (n_d != p.d.n) g |= KD_BAD;      // a delta row whose key is outside the keyset
     if (n_chg > p.cap) g |= KD_CAP;     // the caller's changed-key buffer is too small
-    p.d_counts[0] = n_e;
-    p.d_counts[2] = n_chg;
-    p.d_counts[3] = n_rows;
-    p.d_counts[4] = g;
-    p.d_counts[5] = (carry[6] & KD_MOVED) ? 1 : 0;
-    p.d_counts[6] = n_ak;
-    p.d_counts[7] = carry[5];
+    p.d_counts[KC_EDIT] = n_e;
+    p.d_counts[KC_CHANGED] = n_chg;
+    p.d_counts[KC_ROWS] = n_rows;
+    p.d_counts[KC_GUARD] = g;
+    p.d_counts[KC_MOVED] = (carry[6] & KD_MOVED) ? 1 : 0;
+    p.d_counts[KC_TAKEN] = n_ak;
+    p.d_counts[KC_DKEYS] = carry[5];
   }
   KDSTAMP(0, 7);
 }

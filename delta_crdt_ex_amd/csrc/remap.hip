@@ -20,18 +20,6 @@ namespace {
 constexpr int RB = 256;
 constexpr int RLDS = 2048;  // table entries staged in LDS (16 KB)
 
-__device__ __forceinline__ u64 lower_bound_u64(const u64* t, u64 n, u64 x) {
-  u64 lo = 0, hi = n;
-  while (lo < hi) {
-    const u64 mid = (lo + hi) >> 1;
-    if (t[mid] < x)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(RB) void remap_values_kernel(u64* val, u64 n, const u64* old_ids,
                                                           const u64* new_ids, u64 n_ids, u32* err) {
   __shared__ u64 s_old[RLDS];
@@ -42,7 +30,7 @@ __global__ __launch_bounds__(RB) void remap_values_kernel(u64* val, u64 n, const
   }
   for (u64 i = (u64)blockIdx.x * RB + threadIdx.x; i < n; i += (u64)gridDim.x * RB) {
     const u64 v = val[i];
-    const u64 j = staged ? lower_bound_u64(s_old, n_ids, v) : lower_bound_u64(old_ids, n_ids, v);
+    const u64 j = staged ? lower_bound(s_old, 0, n_ids, v) : lower_bound(old_ids, 0, n_ids, v);
     const bool inside = j < n_ids && (j > 0 || v == (staged ? s_old[0] : old_ids[0]));
     if (!inside) continue;  // outside the relabelled region: unchanged
     if ((staged ? s_old[j] : old_ids[j]) == v)

@@ -24,11 +24,11 @@
 //      per bucket, the tree's shard) BEFORE anything is written
 //   6. writes: the edit's rows in place when no key's row count changed; else straight to
 //      their places in the spare store with the per-key splice index (end, shift) that the
-//      tail kernel's copy tiles search (merkle.hip small_tail_kernel: the state's other rows
+//      tail kernel's copy tiles search (small_tail_kernel below: the state's other rows
 //      into the spare), or -- a state of more than SMALL_COPY_TILES tiles -- as the edit
-//      for the splice kernels after the wait; the union context, the bucket nodes, counts,
-//      dirty chunks and chunk-index deltas (the tail kernel re-reduces the dirty chunks:
-//      MerkleMap.update_hashes), and the result block.
+//      for the splice kernels after the wait; the union context, the changed buckets' nodes,
+//      counts and paths to the root (tree_paths: MerkleMap.update_hashes), the chunk index,
+//      and the result block.
 // Anything outside the limits sets SMALL_FALLBACK before any write: the caller then runs
 // the general path on the untouched state.
 //
@@ -200,20 +200,6 @@ __device__ __forceinline__ u32 delta_bound(const SmallLds& s, u32 nd, u64 k, boo
   return lo;
 }
 
-__device__ __forceinline__ u64 bucket_of_t(const MerkleT& t, u64 key) { return (key << t.sb) >> (64 - t.depth); }
-
-__device__ __forceinline__ u64 row_h(const MerkleT& t, const Row& r) {
-  return row_hash(r.key, th_val(t.th, r.val), r.ts, th_node(t.th, r.node), r.cnt);
-}
-
-__device__ __forceinline__ void put_row(const RowsOut& o, u64 i, const Row& r) {
-  o.key[i] = r.key;
-  o.val[i] = r.val;
-  o.ts[i] = r.ts;
-  o.node[i] = r.node;
-  o.cnt[i] = r.cnt;
-}
-
 // The per-key merge of step 3: calls emit(row) for every kept row in order; returns
 // (kept rows, changed)
 template <class F>
@@ -300,7 +286,7 @@ __device__ __forceinline__ void tree_paths(const SmallArgs& p, SmallLds& s, bool
   __syncthreads();
   const u32 pre = block_excl_scan<NT>(dirty ? (u32)drows : 0u, s.wave, &dtot);
   if (dirty) {
-    s.pb[i] = bucket_of_t(t, s.key[tid]);
+    s.pb[i] = bucket_of(t, s.key[tid]);
     s.pv[0][i] = v0;
     s.pp[i] = (int)pre;
   }
@@ -495,7 +481,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   u64 t_old = 0;
   u32 t_cnt = 0;
   if ((u32)tid < nk && p.has_tree) {
-    const u64 b = bucket_of_t(p.t, p.keys[tid]);
+    const u64 b = bucket_of(p.t, p.keys[tid]);
     t_old = p.t.nodes[((1ull << p.t.depth) - 1) + b];
     t_cnt = p.t.counts[b];
   }
@@ -503,7 +489,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   const bool one_path = nk == 1 && p.has_tree;  // (uniform)
   u64 psib[TMAXD];
   if (one_path && tid < WAVE) {
-    const u64 b = bucket_of_t(p.t, p.keys[0]);
+    const u64 b = bucket_of(p.t, p.keys[0]);
 #pragma unroll
     for (int l = 0; l < TMAXD; l++) psib[l] = p.t.nodes[sib_at(p.t.depth, b, l)];
   }
@@ -662,22 +648,22 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   // (leaf[u]: Σ row_hash of the key's new rows - of its old rows)
   if (!fallback && p.has_tree && (u32)tid < nk && chg) {
     u64 h = 0;
-    for (u32 i = s.aoff[tid]; i < s.aoff[tid + 1]; i++) h -= row_h(p.t, lds_a(s, i));
+    for (u32 i = s.aoff[tid]; i < s.aoff[tid + 1]; i++) h -= rh_row(p.t.th, lds_a(s, i));
     bool c;
     merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c,
-              [&](const Row& r) { h += row_h(p.t, r); });
+              [&](const Row& r) { h += rh_row(p.t.th, r); });
     s.leaf[tid] = h;
   }
   __syncthreads();
   if (!fallback && p.has_tree && (u32)tid < nk) {
     const u64 k = s.key[tid];
     const MerkleT& t = p.t;
-    const u64 b = bucket_of_t(t, k);
-    const bool head = tid == 0 || bucket_of_t(t, s.key[tid - 1]) != b;
+    const u64 b = bucket_of(t, k);
+    const bool head = tid == 0 || bucket_of(t, s.key[tid - 1]) != b;
     if (chg && t.sb && (k >> (64 - t.sb)) != t.shard) atomicOr(&s.flags, MERKLE_ERR_SHARD);
     if (head) {  // the bucket's keys: this one and the next ones in the same bucket
       i64 drows = 0;
-      for (u32 u = tid; u < nk && bucket_of_t(t, s.key[u]) == b; u++) drows += (i64)s.ne[u] - (i64)s.na[u];
+      for (u32 u = tid; u < nk && bucket_of(t, s.key[u]) == b; u++) drows += (i64)s.ne[u] - (i64)s.na[u];
       const i64 now = (i64)t_cnt + drows;
       if (now < 0 || now > 0xFFFF) atomicOr(&s.flags, MERKLE_ERR_COUNT);
     }
@@ -715,12 +701,12 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     const RowsOut rr{rk, rk + SE, (i64*)(rk + 2 * SE), (u32*)(rk + 4 * SE), rk + 3 * SE};
     merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
       if (!moved)
-        put_row(p.aw, a0 + j, r);  // in place: every key keeps its row count
+        store_row(p.aw, a0 + j, r);  // in place: every key keeps its row count
       else if (p.splice_here)
-        put_row(p.sp, (u64)((i64)(e0 + j) + gap), r);  // straight to its place in the spare
+        store_row(p.sp, (u64)((i64)(e0 + j) + gap), r);  // straight to its place in the spare
       else
-        put_row(p.e, e0 + j, r);  // the edit, for the splice kernels after the wait
-      if (chg) put_row(rr, r0 + j, r);  // the changed keys' rows, for the caller
+        store_row(p.e, e0 + j, r);  // the edit, for the splice kernels after the wait
+      if (chg) store_row(rr, r0 + j, r);  // the changed keys' rows, for the caller
       j++;
     });
     if (moved && p.splice_here) {  // the index the tail kernel's splice tiles search
@@ -743,13 +729,13 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     if (tid == 0) p.a_off[nk] = n_ak;
     if (p.has_tree) {
       const MerkleT& t = p.t;
-      const u64 k = s.key[tid], b = bucket_of_t(t, k);
-      const bool head = tid == 0 || bucket_of_t(t, s.key[tid - 1]) != b;
+      const u64 k = s.key[tid], b = bucket_of(t, k);
+      const bool head = tid == 0 || bucket_of(t, s.key[tid - 1]) != b;
       if (head) {  // the bucket's keys: this one and the next ones in the same bucket
         u64 dh = 0;
         i64 drows = 0;
         bool any = false;
-        for (u32 u = tid; u < nk && bucket_of_t(t, s.key[u]) == b; u++) {
+        for (u32 u = tid; u < nk && bucket_of(t, s.key[u]) == b; u++) {
           drows += (i64)s.ne[u] - (i64)s.na[u];
           const bool cu = (u + 1 < nk ? s.coff[u + 1] : n_chg) != s.coff[u];  // key u changed
           if (cu) {

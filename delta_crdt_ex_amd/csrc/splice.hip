@@ -56,17 +56,6 @@ __device__ __forceinline__ u64 wave_upper(const u64* a, u64 n, u64 x) {
   return lo + (u64)__popcll(__ballot(le));
 }
 
-__device__ __forceinline__ u64 lower_bound(const u64* a, u64 lo, u64 hi, u64 x) {
-  while (lo < hi) {
-    const u64 m = (lo + hi) >> 1;
-    if (a[m] < x)
-      lo = m + 1;
-    else
-      hi = m;
-  }
-  return lo;
-}
-
 // ---- locate (the take's first half by streaming): one workgroup per LT state rows
 // stages the tile's keys in LDS (coalesced, 16 KB) and finds, for every keyset key whose
 // first row >= it lies in the tile -- keys in (key[i0 - 1], key[i1 - 1]], the last tile

@@ -380,7 +380,7 @@ uint64_t ref_node_hash(uint64_t left, uint64_t right) {
   return mix64(left ^ mix64(right ^ 0xD6E8FEB86659FD93ULL));
 }
 
-/* The MerkleMap role (csrc/merkle.hip, include/deltagpu.h dg_merkle): the tree over the
+/* The MerkleMap role (csrc/dg_tree.h, include/deltagpu.h dg_merkle): the tree over the
  * keys whose top `sb` bits equal `shard`, 2^depth buckets by the next depth bits;
  * bucket = Σ row hashes of its rows (a key's leaf = Σ over its rows, the raw per-key
  * value map, causal_crdt.ex:392), parents = ref_node_hash(children).  `nodes` holds

@@ -1,4 +1,4 @@
-"""The MerkleMap role on the GPU (csrc/merkle.hip) against the C oracle
+"""The MerkleMap role on the GPU (csrc/merkle_build.hip, merkle_diff.hip, merkle_cont.hip) against the C oracle
 (oracle/deltaref.c ref_merkle_build, oracle/ref.py): build, incremental
 put/delete + update_hashes from a join's changed keys (causal_crdt.ex:383-394),
 the truncating diff (max_sync_size, :98,105,206-214), the partial-diff ping-pong

@@ -1,6 +1,9 @@
 # A/B of a library build against the base on the bench's own numbers, alternating:
 #   bash tools/ab_bench.sh <variant .so under ab/> [bench args]
 # Logs go to $DG_OUT/abb (default _out/abb in the repository).
+# The bench's `mutate` and `anti_entropy_hops` figures come from c_src/_build/bench_mutate and
+# bench_hop, which load the in-tree library through their run path in every step: A/B those
+# by running them with the variant's directory first on LD_LIBRARY_PATH.
 set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 V=$1; shift
