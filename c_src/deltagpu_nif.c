@@ -36,7 +36,12 @@
  *        a batch of {:add, key, value, ts} / {:remove, key} ops by `node` as ONE delta
  *        (dg_mutate_batch, aw_lww_map.ex:99-146) applied like join_delta with the
  *        touched keys (the queued mutations of a GPU-attached replica)
- *   read(state, version, keys | :all)                  -> {:ok, %{key => value}}  (:211-224)
+ *   join_deltas(state, version, [{dots, value, keys}])  -> {:ok, version', new_dots, changed}
+ *   join_deltas_diffs(state, version, [{dots, value, keys}])
+ *                                                      -> {:ok, version', new_dots, changed, diffs}
+ *        the pending {:diff, delta, keys} messages of the mailbox joined in one call
+ *        (dg_join_deltas); changed and diffs are NET over the batch
+ *   read(state, version, keys | :all)                 -> {:ok, %{key => value}}  (:211-224)
  *   take(state, version, keys)                         -> {:ok, value map}  (Map.take, :118,331)
  *   merkle_build(state, version, depth)                -> :ok
  *   merkle_prepare(state, version, levels)             -> {:continue, cont}     (:255)
@@ -346,11 +351,12 @@ static int mapset_map(ErlNifEnv* env, ERL_NIF_TERM set, ERL_NIF_TERM* map) {
   return enif_get_map_value(env, set, A_MAP, map);
 }
 
-/* walk %{key => %{{v, ts} => MapSet[{node, counter}]}} in map order into host rows */
-static int marshal_value(ErlNifEnv* env, engine_res* g, ERL_NIF_TERM value, dgm_rows* out) {
-  ErlNifMapIterator ki, ei, di;
-  ERL_NIF_TERM key, entries, vt, dots, dmap, dot, unused;
-  /* pass 1: intern every value first (a relabel re-spaces ids already handed out) */
+/* every value of %{key => %{{v, ts} => dots}} interned (a relabel re-spaces ids already handed
+ * out, so this runs before any row that holds an id is written: for a batch of deltas, over
+ * every delta before the first one's rows) */
+static int intern_values(ErlNifEnv* env, engine_res* g, ERL_NIF_TERM value) {
+  ErlNifMapIterator ki, ei;
+  ERL_NIF_TERM key, entries, vt, dots;
   if (!enif_map_iterator_create(env, value, &ki, ERL_NIF_MAP_ITERATOR_FIRST)) return DG_E_INVAL;
   for (; enif_map_iterator_get_pair(env, &ki, &key, &entries); enif_map_iterator_next(env, &ki)) {
     if (!enif_map_iterator_create(env, entries, &ei, ERL_NIF_MAP_ITERATOR_FIRST)) return DG_E_INVAL;
@@ -367,6 +373,16 @@ static int marshal_value(ErlNifEnv* env, engine_res* g, ERL_NIF_TERM value, dgm_
     enif_map_iterator_destroy(env, &ei);
   }
   enif_map_iterator_destroy(env, &ki);
+  return DG_OK;
+}
+
+/* walk %{key => %{{v, ts} => MapSet[{node, counter}]}} in map order into host rows */
+static int marshal_value(ErlNifEnv* env, engine_res* g, ERL_NIF_TERM value, dgm_rows* out) {
+  ErlNifMapIterator ki, ei, di;
+  ERL_NIF_TERM key, entries, vt, dots, dmap, dot, unused;
+  /* pass 1: intern every value first */
+  const int rc1 = intern_values(env, g, value);
+  if (rc1) return rc1;
   /* pass 2: the rows */
   enif_map_iterator_create(env, value, &ki, ERL_NIF_MAP_ITERATOR_FIRST);
   for (; enif_map_iterator_get_pair(env, &ki, &key, &entries); enif_map_iterator_next(env, &ki)) {
@@ -756,6 +772,88 @@ static ERL_NIF_TERM join_delta_diffs(ErlNifEnv* env, int argc, const ERL_NIF_TER
   return join_delta_impl(env, argv, 1);
 }
 
+/* join_deltas(state, version, [{dots, value, keys}, ...]) -> {:ok, version', new_dots, changed}
+ * The pending {:diff, delta, keys} messages of a replica's mailbox joined in ONE call
+ * (dgr_join_deltas: one packed message, one fold over the state, the diff of the state before
+ * and after): `changed` is the batch's NET change, and join_deltas_diffs' `diffs` are net too
+ * -- a key is reported once, with its read before the first and after the last delta; the
+ * callbacks the reference would have made per delta are not reproduced. */
+static ERL_NIF_TERM join_deltas_impl(ErlNifEnv* env, const ERL_NIF_TERM argv[], int with_diffs) {
+  state_res* s;
+  uint64_t version;
+  unsigned k = 0;
+  if (!get_state(env, argv[0], argv[1], &s, &version) || !enif_get_list_length(env, argv[2], &k))
+    return enif_make_badarg(env);
+  engine_res* g = s->eng;
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  const unsigned kk = k ? k : 1;
+  dgm_rows* h = (dgm_rows*)enif_alloc(kk * sizeof *h);
+  dg_store* st = (dg_store*)enif_alloc(kk * sizeof *st);
+  dg_context* cx = (dg_context*)enif_alloc(kk * sizeof *cx);
+  uint64_t** keys = (uint64_t**)enif_alloc(kk * sizeof *keys);
+  uint64_t* n_keys = (uint64_t*)enif_alloc(kk * sizeof *n_keys);
+  unsigned n_init = 0;
+  dgr_changed c;
+  ERL_NIF_TERM r = A_NIL, head, tail;
+  if (!h || !st || !cx || !keys || !n_keys) TRY(DG_E_NOMEM);
+  for (unsigned i = 0; i < kk; i++) keys[i] = NULL;
+  /* every delta's values first, then the rows (intern_values) */
+  for (tail = argv[2]; enif_get_list_cell(env, tail, &head, &tail);) {
+    int ar;
+    const ERL_NIF_TERM* e;
+    if (!enif_get_tuple(env, head, &ar, &e) || ar != 3) TRY(DG_E_INVAL);
+    TRY(intern_values(env, g, e[1]));
+  }
+  for (tail = argv[2]; enif_get_list_cell(env, tail, &head, &tail); n_init++) {
+    int ar;
+    const ERL_NIF_TERM* e;
+    enif_get_tuple(env, head, &ar, &e);
+    TRY(dgm_rows_init(&h[n_init], 256, 16));
+    const unsigned i = n_init;
+    rc = marshal_dots(env, g, e[0], &h[i]);
+    if (!rc) rc = marshal_value(env, g, e[1], &h[i]);
+    if (!rc) rc = marshal_keys(env, g, e[2], &keys[i], &n_keys[i]);
+    st[i] = h[i].s;
+    cx[i] = h[i].c;
+    if (rc) {
+      n_init++;
+      goto out;
+    }
+  }
+  if (dgr_state_has_tree(s->s)) TRY(refresh_terms(g));
+  if (with_diffs) {
+    dgr_diffs d;
+    TRY(dgr_join_deltas_diffs(s->s, version, (int)k, st, cx, (const uint64_t* const*)keys, n_keys, &c, &d));
+    TRY(changed_result(env, g, &c, &d, &r));
+  } else {
+    TRY(dgr_join_deltas(s->s, version, (int)k, st, cx, (const uint64_t* const*)keys, n_keys, &c));
+    TRY(changed_result(env, g, &c, NULL, &r));
+  }
+out:
+  if (rc) r = error_term(env, rc);
+  for (unsigned i = 0; i < n_init; i++) dgm_rows_free(&h[i]);
+  for (unsigned i = 0; keys && i < kk; i++)
+    if (keys[i]) enif_free(keys[i]);
+  if (h) enif_free(h);
+  if (st) enif_free(st);
+  if (cx) enif_free(cx);
+  if (keys) enif_free(keys);
+  if (n_keys) enif_free(n_keys);
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
+static ERL_NIF_TERM join_deltas_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return join_deltas_impl(env, argv, 0);
+}
+
+static ERL_NIF_TERM join_deltas_diffs_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return join_deltas_impl(env, argv, 1);
+}
+
 /* mutate_batch(state, version, node, ops) -> {:ok, version', new_dots, changed}: a batch of
  * mutations by `node` -- ops = [{:add, key, value, ts} | {:remove, key}] in the order they
  * were made (the queued mutations of a GPU-attached replica, causal_crdt.ex:196-198,
@@ -1074,6 +1172,8 @@ static ErlNifFunc funcs[] = {
     {"mutate_batch", 4, mutate_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"join_delta_diffs", 5, join_delta_diffs, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"mutate_batch_diffs", 4, mutate_batch_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"join_deltas", 3, join_deltas_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"join_deltas_diffs", 3, join_deltas_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"read", 3, read_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"take", 3, take_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_build", 3, merkle_build_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},

@@ -37,6 +37,13 @@ struct dgr_engine {
   /* a delta sorted on the device when the map walk did not give the order */
   dg_store drows;
   dg_context dctx;
+  /* a batch of deltas (dgr_join_deltas): the device views of each delta's rows, context
+   * and keyset inside the message (or inside drows / dctx, once sorted) */
+  dg_store* b_rows;
+  dg_context* b_ctx;
+  const uint64_t** b_keys;
+  uint64_t* b_nk;
+  uint64_t b_cap;
   /* dg_mutate_batch's delta, its dot list and touched keys */
   dg_store mrows;
   dg_context mctx;
@@ -241,11 +248,12 @@ static dg_context host_ctx(const dgr_engine* g, const dg_context* d) {
 static uint64_t rows_words(uint64_t n) { return 4 * even(n) + even((n + 1) / 2); }
 static uint64_t ctx_words(uint64_t n) { return even(n) + even((n + 1) / 2); }
 
-/* host rows into msg at word o; *dev = the device view of the same place */
-static uint64_t pack_rows(dgr_engine* g, uint64_t o, const dg_store* r, dg_store* dev) {
+/* host rows into the message `hb` at word o; *dev = the view of the same place in its
+ * device copy `db` */
+static uint64_t pack_rows_at(uint64_t* hb, uint64_t* db, uint64_t o, const dg_store* r, dg_store* dev) {
   const uint64_t n = r->n, w = even(n);
-  uint64_t* h = g->h_msg + o;
-  uint64_t* d = g->d_msg + o;
+  uint64_t* h = hb + o;
+  uint64_t* d = db + o;
   if (n) {
     memcpy(h, r->key, n * 8);
     memcpy(h + w, r->val, n * 8);
@@ -258,10 +266,10 @@ static uint64_t pack_rows(dgr_engine* g, uint64_t o, const dg_store* r, dg_store
   return o + rows_words(n);
 }
 
-static uint64_t pack_ctx(dgr_engine* g, uint64_t o, const dg_context* c, dg_context* dev) {
+static uint64_t pack_ctx_at(uint64_t* hb, uint64_t* db, uint64_t o, const dg_context* c, dg_context* dev) {
   const uint64_t n = c->n, w = even(n);
-  uint64_t* h = g->h_msg + o;
-  uint64_t* d = g->d_msg + o;
+  uint64_t* h = hb + o;
+  uint64_t* d = db + o;
   if (n) {
     memcpy(h, c->cnt, n * 8);
     memcpy(h + w, c->node, n * 4);
@@ -269,6 +277,37 @@ static uint64_t pack_ctx(dgr_engine* g, uint64_t o, const dg_context* c, dg_cont
   dg_context v = {c->kind, 0, (uint32_t*)(d + w), d, n, n};
   *dev = v;
   return o + ctx_words(n);
+}
+
+static uint64_t pack_rows(dgr_engine* g, uint64_t o, const dg_store* r, dg_store* dev) {
+  return pack_rows_at(g->h_msg, g->d_msg, o, r, dev);
+}
+
+static uint64_t pack_ctx(dgr_engine* g, uint64_t o, const dg_context* c, dg_context* dev) {
+  return pack_ctx_at(g->h_msg, g->d_msg, o, c, dev);
+}
+
+/* The packed message of a batch of k deltas: per delta its rows | its context | its keyset
+ * (sorted, unique, padded to an even number of words), every part at a 16-byte aligned
+ * offset.  Host code only. */
+uint64_t dgr_batch_words(int k, const dg_store* deltas, const dg_context* ctxs, const uint64_t* n_keys) {
+  uint64_t w = 0;
+  for (int i = 0; i < k; i++) w += rows_words(deltas[i].n) + ctx_words(ctxs[i].n) + even(n_keys[i]);
+  return w;
+}
+
+uint64_t dgr_batch_pack(uint64_t* host, uint64_t* dev, int k, const dg_store* deltas, const dg_context* ctxs,
+                        const uint64_t* const* keys, const uint64_t* n_keys, dg_store* rows_v,
+                        dg_context* ctx_v, const uint64_t** keys_v, uint64_t* n_keys_v) {
+  uint64_t o = 0;
+  for (int i = 0; i < k; i++) {
+    o = pack_rows_at(host, dev, o, &deltas[i], &rows_v[i]);
+    o = pack_ctx_at(host, dev, o, &ctxs[i], &ctx_v[i]);
+    n_keys_v[i] = sort_unique(keys[i], n_keys[i], host + o);
+    keys_v[i] = dev + o;
+    o += even(n_keys[i]);
+  }
+  return o;
 }
 
 /* ------------------------------------------------------------ engine */
@@ -317,6 +356,10 @@ int dgr_engine_close(dgr_engine* g) {
   dg_host_free(e, g->h_cstage);
   free(g->h_bin);
   free(g->sw_stores);
+  free(g->b_rows);
+  free(g->b_ctx);
+  free(g->b_keys);
+  free(g->b_nk);
   const int rc = dg_engine_destroy(e);
   free(g);
   return rc;
@@ -536,47 +579,17 @@ static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dc
   return DG_OK;
 }
 
-/* The join of a delta on the device (rows and context sorted, keys ascending unique) into
- * the state, and the result brought home with one wait.  try_small: the small join first. */
-static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dctx, const uint64_t* dkeys,
-                       uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs, int try_small) {
+/* What a join wrote into the return block (n_changed keys at its head, tk and co as the
+ * call left them, dd its diff arrays) as the caller's views.  Rows or a context past the
+ * block: the changed keys (and their diffs) are parked, the block grown, the rows taken
+ * from the joined state and the context copied (the kernels write the page-locked block
+ * directly). */
+static int bring_home(dgr_state* s, uint64_t n_changed, dg_store tk, dg_context co, dg_lww_diffs dd,
+                      dgr_changed* out, dgr_diffs* diffs) {
   dgr_engine* g = s->g;
-  TRY(room_for(s, drows->n, dctx->n));
-  if (try_small) {
-    int done = 0;
-    TRY(apply_small(s, drows, dctx, dkeys, n_keys, out, diffs, &done));
-    if (done) return DG_OK;
-  }
-  /* the changed keys, their rows and the joined context straight into the page-locked
-   * block (dg_join_delta_out: the kernels write it, one wait); rows of the changed keys
-   * past the block (a key with several entries) are taken afterwards */
-  uint64_t S = umax(2 * n_keys + 64, 1);
-  TRY(grow_back(g, S, s->ctx.n + dctx->n));
-  S = g->back_s;
-  uint64_t C = g->back_c;
+  uint64_t S = g->back_s, C = g->back_c;
   uint64_t* hb = g->h_back;
-  dg_store tk = back_rows(hb, S);
-  dg_context co = {DG_CTX_VV, 0, (uint32_t*)(hb + 6 * S + C), hb + 6 * S, 0, C};
-  uint64_t n_changed = 0;
-  int swapped = 0;
-  dg_lww_diffs dd = back_diffs(hb, S, C);
-  const int rc = diffs ? dg_join_delta_diffs(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
-                                             s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk,
-                                             &co, &dd)
-                       : dg_join_delta_out(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
-                                           s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk, &co);
-  s->version++; /* applied, or failed: either way no older struct reads the device again */
-  TRY(rc);
-  if (diffs && dd.cap == 0 && n_changed) {
-    /* the gather behind the committed join failed (deltagpu.h): the old rows survive only
-     * where the join went through the spare store, which still describes them */
-    if (!swapped) return DG_E_DEVICE;
-    dd = back_diffs(hb, S, C);
-    TRY(dg_read_diff(g->e, &s->spare, &s->rows, hb, n_changed, &dd));
-  }
   if (tk.n > tk.cap || co.n > co.cap) {
-    /* park the changed keys (and their diffs), grow the block, take the rows from the
-     * joined state and copy the context (the kernels write the page-locked block directly) */
     const uint64_t nf = (n_changed + 7) / 8; /* the flags' words */
     TRY(grow_msg(g, diffs ? 3 * n_changed + nf + 1 : n_changed + 1));
     memcpy(g->h_msg, hb, n_changed * 8);
@@ -619,6 +632,47 @@ static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dc
     diffs->flags = dd.flags;
   }
   return DG_OK;
+}
+
+/* The join of a delta on the device (rows and context sorted, keys ascending unique) into
+ * the state, and the result brought home with one wait.  try_small: the small join first. */
+static int apply_delta(dgr_state* s, const dg_store* drows, const dg_context* dctx, const uint64_t* dkeys,
+                       uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs, int try_small) {
+  dgr_engine* g = s->g;
+  TRY(room_for(s, drows->n, dctx->n));
+  if (try_small) {
+    int done = 0;
+    TRY(apply_small(s, drows, dctx, dkeys, n_keys, out, diffs, &done));
+    if (done) return DG_OK;
+  }
+  /* the changed keys, their rows and the joined context straight into the page-locked
+   * block (dg_join_delta_out: the kernels write it, one wait); rows of the changed keys
+   * past the block (a key with several entries) are taken afterwards */
+  uint64_t S = umax(2 * n_keys + 64, 1);
+  TRY(grow_back(g, S, s->ctx.n + dctx->n));
+  S = g->back_s;
+  uint64_t C = g->back_c;
+  uint64_t* hb = g->h_back;
+  dg_store tk = back_rows(hb, S);
+  dg_context co = {DG_CTX_VV, 0, (uint32_t*)(hb + 6 * S + C), hb + 6 * S, 0, C};
+  uint64_t n_changed = 0;
+  int swapped = 0;
+  dg_lww_diffs dd = back_diffs(hb, S, C);
+  const int rc = diffs ? dg_join_delta_diffs(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
+                                             s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk,
+                                             &co, &dd)
+                       : dg_join_delta_out(g->e, &s->rows, &s->ctx, drows, dctx, dkeys, n_keys, &s->spare,
+                                           s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &swapped, &tk, &co);
+  s->version++; /* applied, or failed: either way no older struct reads the device again */
+  TRY(rc);
+  if (diffs && dd.cap == 0 && n_changed) {
+    /* the gather behind the committed join failed (deltagpu.h): the old rows survive only
+     * where the join went through the spare store, which still describes them */
+    if (!swapped) return DG_E_DEVICE;
+    dd = back_diffs(hb, S, C);
+    TRY(dg_read_diff(g->e, &s->spare, &s->rows, hb, n_changed, &dd));
+  }
+  return bring_home(s, n_changed, tk, co, dd, out, diffs);
 }
 
 /* dgr_join_delta (diffs NULL) and dgr_join_delta_diffs */
@@ -672,6 +726,105 @@ int dgr_join_delta_diffs(dgr_state* s, uint64_t version, const dg_store* delta, 
                          const uint64_t* keys, uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs) {
   if (!diffs) return DG_E_INVAL;
   return join_delta(s, version, delta, delta_ctx, keys, n_keys, out, diffs);
+}
+
+/* the device views of a batch's deltas, one entry per delta (kept, grown on demand) */
+static int grow_batch(dgr_engine* g, uint64_t k) {
+  if (g->b_cap >= k) return DG_OK;
+  const uint64_t want = umax(k, 2 * g->b_cap) + 4;
+  dg_store* r = (dg_store*)realloc(g->b_rows, want * sizeof *r);
+  if (r) g->b_rows = r;
+  dg_context* c = (dg_context*)realloc(g->b_ctx, want * sizeof *c);
+  if (c) g->b_ctx = c;
+  const uint64_t** p = (const uint64_t**)realloc(g->b_keys, want * sizeof *p);
+  if (p) g->b_keys = p;
+  uint64_t* n = (uint64_t*)realloc(g->b_nk, want * sizeof *n);
+  if (n) g->b_nk = n;
+  if (!r || !c || !p || !n) return DG_E_NOMEM;
+  g->b_cap = want;
+  return DG_OK;
+}
+
+/* dgr_join_deltas (diffs NULL) and dgr_join_deltas_diffs */
+static int join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
+                       const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out, dgr_diffs* diffs) {
+  if (!s || !out || k < 0 || (k && (!deltas || !ctxs || !keys || !n_keys))) return DG_E_INVAL;
+  for (int i = 0; i < k; i++)
+    if (n_keys[i] && !keys[i]) return DG_E_INVAL;
+  if (k == 1) return join_delta(s, version, &deltas[0], &ctxs[0], keys[0], n_keys[0], out, diffs);
+  TRY(check_version(s, version));
+  dgr_engine* g = s->g;
+  /* ONE message and one copy: per delta its rows | context | keyset (sorted, unique) */
+  TRY(grow_batch(g, (uint64_t)k));
+  const uint64_t words = dgr_batch_words(k, deltas, ctxs, n_keys);
+  TRY(grow_msg(g, words + 2));
+  dgr_batch_pack(g->h_msg, g->d_msg, k, deltas, ctxs, keys, n_keys, g->b_rows, g->b_ctx, g->b_keys, g->b_nk);
+  if (words) TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, words * 8));
+  /* deltas the map walk did not give in order are sorted on the device, into one buffer
+   * for all of them (each at an even row offset) */
+  uint64_t n_rows = 0, n_ctx = 0, n_k = 0, un_rows = 0, un_ctx = 0;
+  for (int i = 0; i < k; i++) {
+    n_rows += deltas[i].n;
+    n_ctx += ctxs[i].n;
+    n_k += g->b_nk[i];
+    if (!rows_sorted(&deltas[i])) un_rows += even(deltas[i].n);
+    if (!ctx_sorted(&ctxs[i])) un_ctx += even(ctxs[i].n);
+  }
+  if (un_rows) TRY(grow_store(g, &g->drows, un_rows));
+  if (un_ctx) TRY(grow_ctx(g, &g->dctx, un_ctx));
+  uint64_t ro = 0, co_ = 0;
+  for (int i = 0; i < k; i++) {
+    if (!rows_sorted(&deltas[i])) {
+      const dg_store* b = &g->drows;
+      dg_store v = {b->key + ro, b->val + ro, b->ts + ro, b->node + ro, b->cnt + ro, 0, deltas[i].n};
+      TRY(dg_sort_store(g->e, &g->b_rows[i], &v));
+      g->b_rows[i] = v;
+      ro += even(deltas[i].n);
+    }
+    if (!ctx_sorted(&ctxs[i])) {
+      const dg_context* b = &g->dctx;
+      dg_context v = {ctxs[i].kind, 0, b->node + co_, b->cnt + co_, 0, ctxs[i].n};
+      TRY(dg_sort_context(g->e, &g->b_ctx[i], &v));
+      v.kind = ctxs[i].kind;
+      g->b_ctx[i] = v;
+      co_ += even(ctxs[i].n);
+    }
+  }
+  TRY(room_for(s, n_rows, n_ctx));
+  /* a changed key is a key of a keyset or of a delta row (one carried over from outside
+   * its keyset) */
+  TRY(grow_back(g, n_k + n_rows + 64, s->ctx.n + n_ctx));
+  const uint64_t S = g->back_s, C = g->back_c;
+  uint64_t* hb = g->h_back;
+  dg_store tk = back_rows(hb, S);
+  dg_context co = {DG_CTX_VV, 0, (uint32_t*)(hb + 6 * S + C), hb + 6 * S, 0, C};
+  dg_lww_diffs dd = back_diffs(hb, S, C);
+  uint64_t n_changed = 0;
+  if (k == 0) { /* nothing changes: the context comes home, the version stays */
+    TRY(dg_copy_async(g->e, hb + 6 * S, s->ctx.cnt, s->ctx.n * 8));
+    TRY(dg_copy_async(g->e, hb + 6 * S + C, s->ctx.node, s->ctx.n * 4));
+    TRY(dg_engine_sync(g->e));
+    co.n = s->ctx.n;
+    co.kind = s->ctx.kind;
+    return bring_home(s, 0, tk, co, dd, out, diffs);
+  }
+  const int rc = dg_join_deltas(g->e, &s->rows, &s->ctx, k, g->b_rows, g->b_ctx, g->b_keys, g->b_nk, &s->spare,
+                                s->has_tree ? &s->tree : NULL, hb, S, &n_changed, &tk, &co, diffs ? &dd : NULL);
+  s->version++; /* applied, or failed: either way no older struct reads the device again */
+  TRY(rc);
+  return bring_home(s, n_changed, tk, co, dd, out, diffs);
+}
+
+int dgr_join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
+                    const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out) {
+  return join_deltas(s, version, k, deltas, ctxs, keys, n_keys, out, NULL);
+}
+
+int dgr_join_deltas_diffs(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
+                          const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out,
+                          dgr_diffs* diffs) {
+  if (!diffs) return DG_E_INVAL;
+  return join_deltas(s, version, k, deltas, ctxs, keys, n_keys, out, diffs);
 }
 
 typedef struct {

@@ -138,6 +138,40 @@ int dgr_mutate_batch_diffs(dgr_state* s, uint64_t version, uint32_t node, uint64
                            const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out,
                            dgr_diffs* diffs);
 
+/* update_state_with_delta for a BATCH of k deltas -- the {:diff, delta, keys} messages
+ * pending in a replica's mailbox -- as one call: all k deltas, contexts and keysets (host,
+ * any order, as for dgr_join_delta) go down as ONE packed message and one copy, deltas the
+ * map walk did not give in order are sorted on the device, and dg_join_deltas folds them
+ * into the state (one pass per 64 deltas), diffs the state before and after, updates or
+ * rebuilds the tree and writes the result into the page-locked return block.
+ * out->keys are the batch's NET changes: every key whose rows differ between the state
+ * before and after the whole batch (for sync and mutation deltas, the union of the per-delta
+ * diff/3 results less the keys that changed and changed back).  The diffs are net over the
+ * batch too, as dgr_mutate_batch_diffs' are over its ops: old_val is the read before the
+ * first delta, new_val the read after the last, and the callbacks the reference would have
+ * made per delta are not reproduced (a key whose read went a -> b -> a reports nothing).
+ * Versions are dgr_join_delta's: one step for the batch, DGR_E_STALE for an older struct,
+ * and any error after the device was touched moves the version on.  k == 1 is
+ * dgr_join_delta[_diffs]; k == 0 changes nothing (no keys, the context, the same version). */
+int dgr_join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
+                    const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out);
+int dgr_join_deltas_diffs(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
+                          const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out,
+                          dgr_diffs* diffs);
+
+/* The batch's packed message, host code only (dgr_join_deltas packs with these; the host test
+ * c_src/test_batch.c checks them).  dgr_batch_words: its length in 8-byte words.
+ * dgr_batch_pack: per delta rows | context | keyset written to `host`, every part at an even
+ * word offset (16-byte aligned: columns key | val | ts | cnt | node, then cnt | node, each
+ * padded to an even number of words), the keyset sorted and unique (*n_keys_v[i] entries, its
+ * room the even number of words >= n_keys[i]); rows_v / ctx_v / keys_v: the views of the
+ * same places in `dev`, the message's device copy (n = cap = the delta's).  Returns the
+ * words written, dgr_batch_words' figure. */
+uint64_t dgr_batch_words(int k, const dg_store* deltas, const dg_context* ctxs, const uint64_t* n_keys);
+uint64_t dgr_batch_pack(uint64_t* host, uint64_t* dev, int k, const dg_store* deltas, const dg_context* ctxs,
+                        const uint64_t* const* keys, const uint64_t* n_keys, dg_store* rows_v,
+                        dg_context* ctx_v, const uint64_t** keys_v, uint64_t* n_keys_v);
+
 /* read/1 (all != 0) or read/2 of `keys` (host ids, any order) (aw_lww_map.ex:211-224):
  * the winning value id per key, ascending by key id.  Host views. */
 int dgr_read(dgr_state* s, uint64_t version, int all, const uint64_t* keys, uint64_t n_keys,

@@ -219,6 +219,13 @@ _SIGS = {
                                   C.POINTER(dg_store), C.POINTER(dg_context),
                                   C.POINTER(C.c_void_p), P64, C.POINTER(dg_store),
                                   C.POINTER(dg_context)]),
+    "dg_store_diff": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_store), P64, C.c_uint64,
+                                P64, C.POINTER(dg_store), C.POINTER(dg_lww_diffs)]),
+    "dg_join_deltas": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context), C.c_int,
+                                 C.POINTER(dg_store), C.POINTER(dg_context),
+                                 C.POINTER(C.c_void_p), P64, C.POINTER(dg_store), C.c_void_p, P64,
+                                 C.c_uint64, P64, C.POINTER(dg_store), C.POINTER(dg_context),
+                                 C.POINTER(dg_lww_diffs)]),
     "dg_context_union": (C.c_int, [C.c_void_p, C.POINTER(dg_context), C.POINTER(dg_context),
                                    C.POINTER(dg_context)]),
     "dg_compress_dots": (C.c_int, [C.c_void_p, C.POINTER(dg_context), C.POINTER(dg_context)]),

@@ -20,7 +20,8 @@ update_resident_state_with_delta does the same to a state that stays on the devi
 is joined in place (dg_join_delta_home_diffs for a mutation or a small sync delta, else
 dg_join_delta_diffs: the join, the changed keys, the MerkleMap update and both reads in one
 call) -- the old rows are overwritten, so the reads before the join come out of the join
-itself.
+itself.  update_resident_state_with_deltas takes a batch of pending deltas in one call
+(dg_join_deltas): the one-pass fold, then the streaming diff of the state before and after.
 """
 from __future__ import annotations
 
@@ -119,6 +120,50 @@ def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys,
     return _callback_diffs(U, order, changed, old_val, new_val, flags)
 
 
+def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tree=None):
+    """update_resident_state_with_delta for a batch [(delta, keys), ...] -- the pending
+    {:diff, delta, keys} messages of a replica's mailbox -- as ONE call (Engine.join_deltas:
+    the fold, the changed keys, the MerkleMap step and both reads).  `state` becomes the fold
+    of the joins through `spare`, and the same `diffs` value is returned, NET over the batch:
+    a key is reported once, with its read before the first and after the last delta (a key
+    whose read went a -> b -> a reports nothing; the per-delta callbacks the reference would
+    have made are not reproduced), in the order of each key's first occurrence over the
+    batch's key lists.  A batch of one delta is the single-delta function."""
+    batch = list(batch)
+    if len(batch) == 1:
+        return update_resident_state_with_delta(state, batch[0][0], batch[0][1], spare, tree)
+    U = state.universe
+    eng = M.engine()
+    order, seen, kts = [], set(), []
+    for _, keys in batch:
+        o, kt = _keyset(U, keys)
+        kts.append(kt)
+        for kid, k in o:
+            if kid not in seen:
+                seen.add(kid)
+                order.append((kid, k))
+    if not batch:
+        return None
+    rows, ctx = state.rows, state.ctx
+    need = ctx.n + sum(d.ctx.n for d, _ in batch)
+    if ctx.cap < need:  # room for the union (a resident replica's context grows by doubling)
+        grown = Context.empty(ctx.kind, 2 * need, rows.device)
+        grown.node[: ctx.n].copy_(ctx.node[: ctx.n])
+        grown.cnt[: ctx.n].copy_(ctx.cnt[: ctx.n])
+        ctx.node, ctx.cnt = grown.node, grown.cnt
+    need_rows = rows.n + sum(d.rows.n for d, _ in batch)
+    if spare.cap < need_rows:
+        grown = Store.empty(2 * need_rows, rows.device)
+        for f in ("key", "val", "ts", "node", "cnt"):
+            setattr(spare, f, getattr(grown, f))
+    state._host = None
+    changed, old_val, new_val, flags, _ = eng.join_deltas(rows, ctx, [d.rows for d, _ in batch],
+                                                          [d.ctx for d, _ in batch], kts, spare, tree)
+    if changed.numel() == 0:
+        return None
+    return _callback_diffs(U, order, u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())
+
+
 def apply_ops(state: M.AWLWWMap, ops, node_id):
     """A batch of mutate/3 calls (causal_crdt.ex:337-342 per op) applied as ONE delta:
     (new_state, diffs) as update_state_with_delta/3 would give for the batch's touched
@@ -127,4 +172,5 @@ def apply_ops(state: M.AWLWWMap, ops, node_id):
     return update_state_with_delta(state, delta, keys)
 
 
-__all__ = ["update_state_with_delta", "update_resident_state_with_delta", "apply_ops"]
+__all__ = ["update_state_with_delta", "update_resident_state_with_delta",
+           "update_resident_state_with_deltas", "apply_ops"]

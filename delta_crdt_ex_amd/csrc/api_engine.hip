@@ -296,6 +296,10 @@ int dg_engine_create(int device, void* hip_stream, dg_engine** out) {
     const char* am = getenv("DG_APPLY_MODE");
     if (am && strcmp(am, "fold") == 0) e->apply_mode = 1;
     if (am && strcmp(am, "onepass") == 0) e->apply_mode = 2;
+    const char* tr = getenv("DG_TREE_REBUILD");
+    if (tr && strcmp(tr, "always") == 0) e->tree_rebuild = dg_engine::TREE_ALWAYS;
+    if (tr && strcmp(tr, "never") == 0) e->tree_rebuild = dg_engine::TREE_NEVER;
+    if (tr && atoll(tr) > 0) e->tree_rebuild_div = (u64)atoll(tr);
   }
   int rc = set_device(e);
   if (rc != DG_OK) {

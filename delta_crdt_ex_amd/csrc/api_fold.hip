@@ -167,8 +167,10 @@ int kfold_pass(dg_engine* e, const dg_store* state, const dg_context* ctx, int k
   return DG_OK;
 }
 
+}  // namespace
+
 // dg_apply_deltas: passes of up to KFOLD_MAX_K deltas (each a one-pass fold), or the
-// delta-by-delta fold when an input needs it.
+// delta-by-delta fold when an input needs it.  (dg_join_deltas folds through it too.)
 int apply_deltas(dg_engine* e, const dg_store* state, const dg_context* ctx, int k,
                  const dg_store* deltas, const dg_context* dctxs, const uint64_t* const* keys,
                  const uint64_t* n_keys, dg_store* out, dg_context* out_ctx) {
@@ -211,9 +213,6 @@ int apply_deltas(dg_engine* e, const dg_store* state, const dg_context* ctx, int
   }
   return DG_OK;
 }
-
-
-}  // namespace
 
 extern "C" {
 

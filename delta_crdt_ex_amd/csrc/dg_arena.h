@@ -236,6 +236,22 @@ inline KfoldScratch kfold_layout(Arena& a, uint64_t k, size_t run_bytes, uint64_
   return s;
 }
 
+// The streaming store diff (engine tmp): the diagonals' bounds (4 per diagonal, tiles + 1
+// diagonals) | per tile the changed keys, their rows and the two offsets | the changed mask
+// (u32 words, zeroed per call)
+struct SdiffScratch {
+  uint64_t* bounds;
+  uint64_t *cnt_k, *cnt_r, *off_k, *off_r;
+  uint32_t* mask;
+};
+inline SdiffScratch sdiff_layout(Arena& a, uint64_t tiles, uint64_t mask_words) {
+  SdiffScratch s;
+  s.bounds = a.take<uint64_t>(4 * (tiles + 1));
+  for (uint64_t** q : {&s.cnt_k, &s.cnt_r, &s.off_k, &s.off_r}) *q = a.take<uint64_t>(tiles);
+  s.mask = a.take<uint32_t>(mask_words);
+  return s;
+}
+
 // dg_mutate_batch (engine tmp): the delta's dots (node | cnt) | their sort's second pair |
 // the sort's scratch
 struct MutateScratch {

@@ -71,6 +71,12 @@ struct dg_engine {
   // dg_apply_deltas: 0 one pass per <= 64 deltas, delta by delta where an input needs it;
   // DG_APPLY_MODE=fold: always delta by delta; =onepass: never (DG_E_INVAL instead)
   int apply_mode = 0;
+  // dg_join_deltas' tree step: the incremental update (a searched thread per changed key), or
+  // a rebuild (a stream over the new state) once the batch changed more than
+  // rows / tree_rebuild_div keys.  DG_TREE_REBUILD=always / never / a divisor
+  enum { TREE_BY_SHARE = 0, TREE_ALWAYS = 1, TREE_NEVER = 2 };
+  int tree_rebuild = TREE_BY_SHARE;
+  u64 tree_rebuild_div = 64;
   Buf h_stage;  // pinned staging of kernel descriptors
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // hand-offs to the device's shared join stream
   // asynchronous calls since the last dg_engine_sync, replayed there (joins on the
@@ -142,6 +148,7 @@ enum MarkCount {    // mark.hip
   MK_USED = 0,      // ids used
   MK_UNKNOWN = 1,   // rows whose id is not in the table
 };
+// (the streaming store diff: enum SdCount, dg_launch.h -- its kernels use the names too)
 constexpr int HC_KFOLD_FLAG = 10;  // h_counts only: kfold_pass copies its flag word here
 
 constexpr int RETRY_WORKERS = 32;  // a join's re-run after an aborted grid (with_small_grid)
@@ -220,6 +227,12 @@ int splice_edit(dg_engine* e, Splice* w, const dg_context* ca, const dg_store* b
 // ---- api_join_delta.hip
 int tree_update(dg_engine* e, dg_merkle* t, const dg_store* olds, const dg_store* news, const uint64_t* keys,
                 uint64_t n_keys, const char* what);
+
+// ---- api_fold.hip
+// dg_apply_deltas behind its argument checks: out <- the fold of the k deltas into (state, ctx)
+int apply_deltas(dg_engine* e, const dg_store* state, const dg_context* ctx, int k, const dg_store* deltas,
+                 const dg_context* dctxs, const uint64_t* const* keys, const uint64_t* n_keys, dg_store* out,
+                 dg_context* out_ctx);
 
 // ---- api_merkle.hip
 int merkle_build_enqueue(dg_engine* e, const dg_store* s, dg_merkle* t, uint64_t* d_n_keys);

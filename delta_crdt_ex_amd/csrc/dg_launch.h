@@ -557,4 +557,37 @@ hipError_t launch_leafdiff(const MerkleT& t, const Rows& s, const u64* buckets, 
                            const u64* ph, u64 np, u64* out, u64 cap, u64* scratch, u64* d_count,
                            hipStream_t st);
 
+// ---- sdiff.hip: the streaming diff of two stores (dg_store_diff, dg_join_deltas; see the file header)
+constexpr u64 SDIFF_TILE = 2048;  // merged rows between two diagonals of the split
+constexpr int SDIFF_BLOCK = 512;  // threads of a count / write workgroup
+inline u64 sdiff_tiles(u64 na, u64 nb) { return (na + nb + SDIFF_TILE - 1) / SDIFF_TILE; }
+// u32 words of the changed mask: a bit per merged row, and the words behind the last tile's
+// first that its workgroup reads unconditionally
+inline u64 sdiff_mask_words(u64 na, u64 nb) { return (na + nb) / 32 + SDIFF_TILE / 32 + 4; }
+// the count block d_counts[0..2) of this path (sdiff_scan_kernel writes it; the write kernel
+// and the host read it)
+enum SdCount {
+  SD_KEYS = 0,  // changed keys
+  SD_ROWS = 1,  // their rows in b
+};
+struct SdiffArgs {
+  Rows a, b;           // the old and the new store
+  u64 ntiles;          // sdiff_tiles(a.n, b.n)
+  u64* bounds;         // 4 * (ntiles + 1): per diagonal the boundary key's lo_a, lo_b, hi_a, hi_b
+  u64 *cnt_k, *cnt_r;  // per tile: changed keys, their rows in b
+  u64 *off_k, *off_r;  // ... and their exclusive offsets
+  u32* mask;           // sdiff_mask_words: zeroed by the launch
+  u64 mask_words;
+  u64* changed;        // changed keys (cap), device or mapped host memory, like every output here
+  u64 cap;
+  int has_rows;        // their rows in b into rows[0, rows_cap), unless there are more
+  RowsOut rows;
+  u64 rows_cap;
+  int has_diffs;       // per changed key the read before and after, as launch_read_diff gives them
+  u64 *old_val, *new_val;
+  uint8_t* flags;
+  u64* d_counts;
+};
+hipError_t launch_store_diff(const SdiffArgs& p, hipStream_t st);
+
 }  // namespace dg

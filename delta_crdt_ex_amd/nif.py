@@ -12,6 +12,10 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
     mutate_batch(state, version, node, ops)         -> ("ok", version', new_dots, changed)
     join_delta_diffs(state, version, dots, value, keys)
     mutate_batch_diffs(state, version, node, ops)   -> ("ok", version', new_dots, changed, diffs)
+    join_deltas(state, version, [(dots, value, keys), ...])
+                                                    -> ("ok", version', new_dots, changed)
+    join_deltas_diffs(state, version, [(dots, value, keys), ...])
+                                                    -> ("ok", version', new_dots, changed, diffs)
     read(state, version, keys | "all")              -> ("ok", {key: value})
     take(state, version, keys)                      -> ("ok", value_map)
     merkle_build(state, version, depth)             -> "ok"
@@ -90,6 +94,14 @@ _SIGS = {
                                    C.POINTER(dgr_changed), C.POINTER(dgr_diffs)]),
     "dgr_mutate_batch_diffs": (I32, [VP, U64, C.c_uint32, U64, VP, VP, VP, VP, C.POINTER(dgr_changed),
                                      C.POINTER(dgr_diffs)]),
+    "dgr_join_deltas": (I32, [VP, U64, I32, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP), PU64,
+                              C.POINTER(dgr_changed)]),
+    "dgr_join_deltas_diffs": (I32, [VP, U64, I32, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP),
+                                    PU64, C.POINTER(dgr_changed), C.POINTER(dgr_diffs)]),
+    # (the batch's packing alone, host code: c_src/test_batch.c checks it)
+    "dgr_batch_words": (U64, [I32, C.POINTER(dg_store), C.POINTER(dg_context), PU64]),
+    "dgr_batch_pack": (U64, [VP, VP, I32, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP), PU64,
+                             C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP), PU64]),
     "dgr_read": (I32, [VP, U64, I32, VP, U64, C.POINTER(VP), C.POINTER(VP), PU64]),
     "dgr_take": (I32, [VP, U64, VP, U64, C.POINTER(dg_store)]),
     "dgr_merkle_build": (I32, [VP, U64, C.c_uint32]),
@@ -426,6 +438,49 @@ def join_delta_diffs(state: State, version: int, dots, value, keys):
     return join_delta(state, version, dots, value, keys, _diffs=True)
 
 
+def join_deltas(state: State, version: int, deltas, _diffs: bool = False):
+    """deltas = [(dots, value, keys), ...]: the pending {:diff, delta, keys} messages of a
+    replica's mailbox joined in ONE call (dgr_join_deltas: one packed message, one fold, the
+    diff of the state before and after).  Same return shape as join_delta; `changed` is the
+    batch's net change."""
+    eng = state.engine
+    hs = []
+    for dots, value, _keys in deltas:  # pass 1: every value of the batch (a relabel re-spaces ids)
+        for entries in value.values():
+            for (v, _ts) in entries:
+                eng.universe.value(eng.unwrap(v))
+    for dots, value, keys in deltas:
+        h = _Rows()
+        _marshal_dots(eng, dots, h)
+        _marshal_value(eng, value, h)
+        hs.append((h, _marshal_keys(eng, keys)))
+    if eng.lib.dgr_state_has_tree(state.ptr):
+        rc = eng.refresh_terms()
+        if rc:
+            return _err(rc)
+    k = len(hs)
+    st = (dg_store * max(k, 1))(*[h.store() for h, _ in hs])
+    cx = (dg_context * max(k, 1))(*[h.context() for h, _ in hs])
+    kp = (C.c_void_p * max(k, 1))(*[kid.ctypes.data if len(kid) else None for _, kid in hs])
+    kn = (C.c_uint64 * max(k, 1))(*[len(kid) for _, kid in hs])
+    ch = dgr_changed()
+    if _diffs:
+        df = dgr_diffs()
+        rc = eng.lib.dgr_join_deltas_diffs(state.ptr, version, k, st, cx, kp, kn, C.byref(ch), C.byref(df))
+        return _err(rc) if rc else _diffs_result(eng, ch, df)
+    rc = eng.lib.dgr_join_deltas(state.ptr, version, k, st, cx, kp, kn, C.byref(ch))
+    if rc:
+        return _err(rc)
+    return _changed_result(eng, ch)
+
+
+def join_deltas_diffs(state: State, version: int, deltas):
+    """join_deltas that also returns on_diffs' list, NET over the batch (a key is reported
+    once, with its read before the first and after the last delta; the callbacks the
+    reference would have made per delta are not reproduced)."""
+    return join_deltas(state, version, deltas, _diffs=True)
+
+
 def mutate_batch(state: State, version: int, node, ops, _diffs: bool = False):
     """ops = [("add", key, value, ts) | ("remove", key)] in the order they were made"""
     eng = state.engine
@@ -553,6 +608,6 @@ def resolve_keys(engine: Engine, keys):
 
 
 __all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "join_delta_diffs",
-           "mutate_batch_diffs", "classify_diffs", "read", "take",
+           "mutate_batch_diffs", "join_deltas", "join_deltas_diffs", "classify_diffs", "read", "take",
            "merkle_build", "merkle_prepare", "merkle_continue", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

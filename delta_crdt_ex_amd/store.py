@@ -736,6 +736,106 @@ class Engine:
             return changed[:nch], None, None, None, bool(sw.value)
         return changed[:nch], ov[:nch], nv[:nch], fl[:nch], bool(sw.value)
 
+    def store_diff(self, old: Store, new: Store, want_rows: bool = False, want_diffs: bool = False,
+                   changed: torch.Tensor | None = None, rows: Store | None = None):
+        """The streaming diff of two stores (dg_store_diff): every key whose rows differ
+        between `old` and `new`, ascending.  Returns the changed keys alone, or a tuple
+        (changed[, rows][, (old_val, new_val, flags)]) with the changed keys' rows of `new`
+        (want_rows) and their LWW reads on either side (want_diffs).  `changed` / `rows`: the
+        caller's own buffers (too small a `changed` raises CapacityError)."""
+        self._order()
+        if changed is None:
+            changed = torch.empty(max(old.n + new.n, 1), dtype=_I64, device=self.device)
+        cap = int(changed.numel())
+        if want_rows and rows is None:
+            rows = Store.empty(max(new.n, 1), self.device)
+        ro = rows.abi() if want_rows else None
+        if want_diffs:
+            ov, nv, fl, d = self._diffs(cap)
+        so, sn = old.abi(), new.abi()
+        n = C.c_uint64(0)
+        check(self.lib.dg_store_diff(self.h, C.byref(so), C.byref(sn), _ptr(changed, _abi.P64), cap, C.byref(n),
+                                     C.byref(ro) if ro is not None else None,
+                                     C.byref(d) if want_diffs else None))
+        nch = int(n.value)
+        out = [changed[:nch]]
+        if want_rows:
+            rows.n = int(ro.n)
+            if rows.n > rows.cap:
+                raise _abi.CapacityError(_abi.DG_E_CAPACITY, f"store_diff: {rows.n} rows > cap {rows.cap}")
+            out.append(rows)
+        if want_diffs:
+            out.append((ov[:nch], nv[:nch], fl[:nch]))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def join_deltas(self, state: Store, state_ctx: Context, deltas, dctxs, keys, spare: Store,
+                    tree: MerkleTree | None = None, changed: torch.Tensor | None = None,
+                    rows: Store | None = None, diffs: _abi.dg_lww_diffs | None = None,
+                    ctx_out: Context | None = None):
+        """CausalCrdt.update_state_with_delta for a batch of deltas on a device-resident state
+        (dg_join_deltas): `state` and `state_ctx` become the fold of join(state, deltas[i],
+        keys[i]) (keys as for apply_deltas), `tree` follows, and the changed keys are the
+        batch's NET change with their LWW reads before and after the batch.  With at least one
+        delta the result lands in `spare` and the two Store objects exchange their columns;
+        `spare` then holds the old rows (n = 0, as after join_delta).  Returns what
+        join_delta_diffs returns: (changed keys, old_val, new_val, flags, swapped)."""
+        self._order()
+        k = len(deltas)
+        arr_s = (_abi.dg_store * max(k, 1))(*[d.abi() for d in deltas])
+        arr_c = (_abi.dg_context * max(k, 1))(*[c.abi() for c in dctxs])
+        kp = kn = None
+        if keys is not None:
+            kp = (C.c_void_p * max(k, 1))(*[C.c_void_p(t.data_ptr() if t is not None and t.numel()
+                                                         else 0) for t in keys])
+            kn_np = np.array([int(t.numel()) if t is not None else 0 for t in keys] or [0], np.uint64)
+            kn = kn_np.ctypes.data_as(_abi.P64)
+            # (an empty keyset is a join over no keys, not a full-state join: see apply_deltas)
+            dummy = torch.zeros(1, dtype=_I64, device=self.device)
+            for i, t in enumerate(keys):
+                if t is not None and t.numel() == 0:
+                    kp[i] = C.c_void_p(dummy.data_ptr())
+        if changed is None:
+            full = keys is None or any(t is None for t in keys)
+            bound = sum(d.n for d in deltas) + (state.n if full else sum(int(t.numel()) for t in keys))
+            changed = torch.empty(max(bound, 1), dtype=_I64, device=self.device)
+        cap = int(changed.numel())
+        own = diffs is None
+        if own:
+            ov, nv, fl, d = self._diffs(cap)
+        else:
+            ov = nv = fl = None
+            d = diffs
+        ss, sc, sp = state.abi(), state_ctx.abi(), spare.abi()
+        t = tree.abi() if tree is not None else None
+        ro = rows.abi() if rows is not None else None
+        co = ctx_out.abi() if ctx_out is not None else None
+        n = C.c_uint64(0)
+        check(self.lib.dg_join_deltas(
+            self.h, C.byref(ss), C.byref(sc), k, arr_s, arr_c, kp, kn, C.byref(sp),
+            C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n),
+            C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None, C.byref(d)))
+        if rows is not None:
+            rows.n = int(ro.n)
+        if ctx_out is not None:
+            ctx_out.n, ctx_out.kind = int(co.n), int(co.kind)
+        swapped = k > 0
+        if swapped:
+            for f in ("key", "val", "ts", "node", "cnt"):
+                a, b = getattr(state, f), getattr(spare, f)
+                setattr(state, f, b)
+                setattr(spare, f, a)
+            spare.n = 0
+        state.n = int(ss.n)
+        state_ctx.n = int(sc.n)
+        state_ctx.kind = int(sc.kind)
+        if tree is not None:
+            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
+            tree.store = state
+        nch = int(n.value)
+        if not own:
+            return changed[:nch], None, None, None, swapped
+        return changed[:nch], ov[:nch], nv[:nch], fl[:nch], swapped
+
     def home_block(self):
         """The page-locked result block of join_delta_home / join_delta_home_diffs as a numpy
         view (DG_HOME_DIFFS_WORDS words; the plain call writes a prefix of it)."""

@@ -396,6 +396,56 @@ int dg_apply_deltas(dg_engine* e, const dg_store* state, const dg_context* ctx, 
                     const uint64_t* const* keys, const uint64_t* n_keys, dg_store* out,
                     dg_context* out_ctx);
 
+/* The streaming diff of two sorted unique stores: every key whose rows differ between
+ * old_s and new_s -- in any of the five columns, or in their number -- ascending and unique
+ * into changed[0, cap), *n_changed = their number (DG_E_CAPACITY if > cap; *n_changed is
+ * set then too).  diffs (NULL: none; cap >= `cap`): entry i holds the LWW read of changed[i]
+ * in old_s and in new_s, as dg_lww_diffs describes it (the greatest ts, a tie going to the
+ * first row).  rows (NULL: none): the changed keys' rows of new_s in store order,
+ * rows->n = their number; more than rows->cap are not written, as for dg_join_delta_rows.
+ * Both stores are streamed once or twice; no key is searched in a whole column, and runs of
+ * any length and any key distribution are handled.  changed, rows and the diff arrays may be
+ * device memory or memory from dg_host_alloc.  Synchronous. */
+int dg_store_diff(dg_engine* e, const dg_store* old_s, const dg_store* new_s, uint64_t* changed,
+                  uint64_t cap, uint64_t* n_changed, dg_store* rows, dg_lww_diffs* diffs);
+
+/* CausalCrdt.update_state_with_delta (causal_crdt.ex:383-404) for a BATCH of k deltas on a
+ * device-resident state: what a replica whose mailbox holds k {:diff, delta, keys} messages
+ * does with them, in one call.
+ *   state      becomes join(...join(state, deltas[0], keys[0])..., deltas[k-1], keys[k-1]),
+ *              exactly dg_apply_deltas' result (one pass per 64 deltas, or step by step:
+ *              see there), and state_ctx the union of the contexts.
+ *   changed    every key whose rows differ between the state before and after the batch
+ *              (dg_store_diff of the two), ascending: the batch's NET change.  For sync- and
+ *              mutation-shaped deltas -- every delta row's key is in that delta's keyset, the
+ *              only shapes CausalCrdt makes -- this is the union of the reference's per-delta
+ *              diff/3 results less the keys that changed and changed back.  For any other
+ *              shape it is a superset of that: it also holds the keys carried over from
+ *              outside the keysets.  Either way the tree equals a rebuild.
+ *   diffs      (NULL: none; cap >= `cap`) the LWW reads of changed[i] before and after the
+ *              BATCH.  on_diffs is net over the batch, as for dg_mutate_batch: a key whose
+ *              read went a -> b -> a reports nothing, and the callbacks the reference would
+ *              have made per delta are not reproduced.
+ *   rows       (NULL: none) the changed keys' rows in the joined state, rows->n their number;
+ *              more than rows->cap are not written.  ctx_out (NULL: none): a copy of the
+ *              joined context (more than ctx_out->cap entries: not written).
+ *   tree       (NULL: none) afterwards bit-identical to dg_merkle_build of the joined state:
+ *              the incremental update of the changed keys, or -- when the batch changed more
+ *              than 1/64 of the state's rows -- a rebuild (DG_TREE_REBUILD=always / never /
+ *              a divisor in the environment at engine creation).
+ * spare->cap >= state->n + Σ deltas[i].n and state_ctx->cap >= state_ctx->n + Σ dctxs[i].n
+ * (DG_E_CAPACITY); diffs->cap >= cap (DG_E_INVAL).  For k >= 1 the joined state is always
+ * written to `spare` and the two dg_store structs are exchanged: on return *state describes
+ * the joined state and *spare the old one (its rows and n intact).  k == 0 changes nothing
+ * and gives *n_changed = 0.  All or nothing: on any error return -- more changed keys than
+ * `cap` and a tree input error included -- the state, its context and the tree are as they
+ * were.  changed, rows, ctx_out and the diff arrays may be memory from dg_host_alloc.
+ * Synchronous. */
+int dg_join_deltas(dg_engine* e, dg_store* state, dg_context* state_ctx, int k, const dg_store* deltas,
+                   const dg_context* dctxs, const uint64_t* const* keys, const uint64_t* n_keys,
+                   dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
+                   uint64_t* n_changed, dg_store* rows, dg_context* ctx_out, dg_lww_diffs* diffs);
+
 /* ---- sync deltas ----------------------------------------------------------- */
 /* The value half of a sync delta, Map.take(state.value, keys) (causal_crdt.ex:112-123,
  * 324-335: {:diff, %{state | dots: diff.dots, value: Map.take(value, keys)}, keys}):
