@@ -374,18 +374,21 @@ __device__ __forceinline__ void buf_put(Buf& s, int x, u64 key, u64 val, i64 ts,
   s.node[x] = node;
 }
 
-// Global row index of staging slot x, or -1 if the slot is outside the stores:
-// slot x < nat + 2 is a[a0 - 1 + x], slot x >= nat + 2 is b[b0 - 1 + (x - nat - 2)].
-__device__ __forceinline__ i64 slot_row(int x, int nat, u64 a0, u64 b0, u64 na, u64 nb,
+// Staging slot x of a tile: slot x < nat + 2 is a[a0 - 1 + x], slot x >= nat + 2 is
+// b[b0 - 1 + (x - nat - 2)]; the tile has nat + nbt + 4 slots.  Returns the row to LOAD for
+// the slot, for every x, so that the loads need no branch: the slot's own row where it
+// exists, else a row that does -- the index clamped into the store, and the other store
+// when the slot's own is empty (n == 0: its column pointers may be null; a join of two
+// empty stores launches no tile kernel).  The index is below the n of the store *from_b
+// names.
+__device__ __forceinline__ u64 slot_row(int x, int nat, u64 a0, u64 b0, u64 na, u64 nb,
                                         bool* from_b) {
-  if (x < nat + 2) {
-    const i64 g = (i64)a0 - 1 + x;
-    *from_b = false;
-    return (g >= 0 && (u64)g < na) ? g : -1;
-  }
-  const i64 g = (i64)b0 - 1 + (x - (nat + 2));
-  *from_b = true;
-  return (g >= 0 && (u64)g < nb) ? g : -1;
+  const bool in_a = x < nat + 2;
+  const i64 g = in_a ? (i64)a0 - 1 + x : (i64)b0 - 1 + (x - (nat + 2));
+  const bool fb = in_a ? na == 0 : nb != 0;
+  const i64 last = (i64)(fb ? nb : na) - 1;
+  *from_b = fb;
+  return (u64)min(max(g, (i64)0), last);
 }
 
 constexpr int SLOTS = (JS + JB - 1) / JB;
@@ -553,12 +556,15 @@ struct TileLds {
 
 // Register staging of a tile: every lane issues the loads of all its slots (issue_tile)
 // long before it writes them to LDS (commit_tile), so a whole tile streams in while the
-// previous one is merged.
+// previous one is merged.  Both are straight-line code.  Loads or LDS writes under a
+// per-lane `if (slot exists)` put the wait for the staged rows inside a branch, and the
+// compiler, unable to prove at the loop's joins that the staging registers had no load
+// pending, drained the memory pipe (vmcnt 0) before the loads of each slot: the second
+// slot's loads left after the first's had landed, and the merge began after both.
 struct Staged {  // one thread's share of a staged tile, in registers
   u64 k[SLOTS], v[SLOTS], c[SLOTS];
   i64 t[SLOTS];
   u32 n[SLOTS];
-  bool ok[SLOTS];
 };
 
 __device__ __forceinline__ void tile_geom(u64 t, u64 jt, u64 a0, u64 a1, u64 total, int* nat,
@@ -569,33 +575,38 @@ __device__ __forceinline__ void tile_geom(u64 t, u64 jt, u64 a0, u64 a1, u64 tot
   *b0 = d0 - a0;
 }
 
-__device__ __forceinline__ void issue_tile(const Rows& A, const Rows& B, int nat, int nbt, u64 a0,
-                                           u64 b0, Staged& r) {
+// Every lane loads a row for each of its slots: slots without a row load one that exists
+// (slot_row).
+__device__ __forceinline__ void issue_tile(const Rows& A, const Rows& B, int nat, u64 a0, u64 b0,
+                                           Staged& r) {
   const int tid = threadIdx.x;
+  // (by value: a per-lane select between the two structs' fields becomes a load through a
+  // selected address, see load_row_sel)
+  const u64 na = opaque_val(A.n), nb = opaque_val(B.n);
 #pragma unroll
   for (int k = 0; k < SLOTS; k++) {
-    const int x = tid + k * JB;
-    bool fb = false;
-    const i64 g = x < nat + nbt + 4 ? slot_row(x, nat, a0, b0, A.n, B.n, &fb) : -1;
-    r.ok[k] = g >= 0;
-    if (r.ok[k]) {
-      const Row x = load_row_sel(A, B, fb, (u64)g);
-      r.k[k] = x.key;
-      r.v[k] = x.val;
-      r.t[k] = x.ts;
-      r.n[k] = x.node;
-      r.c[k] = x.cnt;
-    }
+    bool fb;
+    const u64 g = slot_row(tid + k * JB, nat, a0, b0, na, nb, &fb);
+    const Row x = load_row_sel(A, B, fb, g);
+    r.k[k] = x.key;
+    r.v[k] = x.val;
+    r.t[k] = x.ts;
+    r.n[k] = x.node;
+    r.c[k] = x.cnt;
   }
 }
 
+// Every lane writes every slot it staged, so the LDS writes -- and the wait for the staged
+// rows before them -- are on every lane's path.  A slot without a row gets the row that
+// issue_tile loaded in its place: the merge never uses such a slot (its validity tests:
+// the global index of a neighbour, nat / nbt for the tile's ends), it held whatever an
+// earlier tile left there before.  Slots past the buffer go to its last row, JS - 1, which
+// no tile uses (a tile has at most JT + 4 slots).
 __device__ __forceinline__ void commit_tile(const Staged& r, Buf& s) {
   const int tid = threadIdx.x;
 #pragma unroll
-  for (int k = 0; k < SLOTS; k++) {
-    const int x = tid + k * JB;
-    if (r.ok[k]) buf_put(s, x, r.k[k], r.v[k], r.t[k], r.n[k], r.c[k]);
-  }
+  for (int k = 0; k < SLOTS; k++)
+    buf_put(s, min(tid + k * JB, JS - 1), r.k[k], r.v[k], r.t[k], r.n[k], r.c[k]);
 }
 
 // ------------------------------------------------------------- single-pass join
@@ -604,10 +615,10 @@ __device__ __forceinline__ void commit_tile(const Staged& r, Buf& s) {
 // so iteration k of every workgroup together covers the stripe of tiles [kG, (k+1)G).
 // Two LDS tile buffers alternate.  Iteration k of workgroup w (tile t = w + kG):
 //   1. commit tile t's rows (prefetched into registers) to buffer k%2;
-//   2. issue the loads of tile t + G into registers, and the loads of stripe k-1's
-//      G tile counts (they stream during the merge);
+//   2. issue the loads of tile t + G into registers (they stream during the merge);
 //   3. merge tile t, block-scan its keep bits: count n_t and compaction list;
-//      publish n_t (an epoch-tagged 32-bit granule, written once);
+//      publish n_t (an epoch-tagged 32-bit granule, written once), then issue the loads
+//      of stripe k-1's G tile counts;
 //   4. offsets of stripe k-1, computed redundantly by every workgroup from its G
 //      counts: tile (w + (k-1)G) starts at base_{k-1} + Σ_{w' < w} n, and
 //      base_k = base_{k-1} + Σ_{all w'} n;
@@ -615,7 +626,7 @@ __device__ __forceinline__ void commit_tile(const Staged& r, Buf& s) {
 //      offset.
 // No look-back chain and no ticket: a stripe's counts were all published one merge
 // earlier, so step 4 rarely waits; its cost is one G-word read per iteration, issued
-// before the merge.  Spins stay bounded (scan.err bit 0 on timeout).
+// behind the tile's own count.  Spins stay bounded (scan.err bit 0 on timeout).
 constexpr int FUSE_IT = 4;  // fused: tiles per workgroup whose splits the kernel searches itself
 // (stripe_sums' partials are double-buffered by iteration parity, which drops the barrier
 // a single buffer needs before its writes: measured neutral, config 5 356-360 vs 358-360 us
@@ -645,8 +656,9 @@ __device__ __forceinline__ void publish_count(u32* cs, u64 t, u32 epoch, u32 n) 
 }
 
 // Stripe counts of tiles [base_t, base_t + G) ∩ [0, ntiles), CQ per thread: issued
-// early (stripe_load), consumed after the merge (stripe_sums), which re-polls the ones
-// not yet published and returns (Σ over workgroups w' < w, Σ over all).
+// behind the tile's own count (stripe_load), consumed after the barrier that follows
+// (stripe_sums), which re-polls the ones not yet published and returns (Σ over workgroups
+// w' < w, Σ over all).
 struct StripeCounts {
   u32 v[CQ];
   bool ready;
@@ -658,9 +670,11 @@ __device__ __forceinline__ void stripe_load(const u32* cs, u64 base_t, u64 G, u6
 #pragma unroll
   for (int q = 0; q < CQ; q++) {
     const u64 x = (u64)threadIdx.x + (u64)q * JB;  // workgroup index within the stripe
-    c.v[q] = epoch << CNT_BITS;                     // absent tiles count 0
-    if (x < G && base_t + x < ntiles)
-      c.v[q] = __hip_atomic_load(cs + base_t + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (every lane loads: an absent tile reads the stripe's first granule, base_t < ntiles;
+    // stripe_sums replaces what it read -- here the select would wait for the load)
+    const bool has = x < G && base_t + x < ntiles;
+    c.v[q] = __hip_atomic_load(cs + base_t + (has ? x : 0), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -701,7 +715,9 @@ __device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 need, const
       absent = true;
   }
   if (!absent) return false;
-  __hip_atomic_store(abort, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // (the epoch again from the argument segment: as a store's data it needs a vector
+  // register, which the compiler otherwise sets aside before the tile loop and spills)
+  __hip_atomic_store(abort, cold(&sc->epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   atomicOr(cold(&sc->err), 2u);
   return true;
 }
@@ -710,9 +726,14 @@ __device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 need, const
 // through its tiles without waiting and writes stay inside the output (whose rows the
 // caller discards).
 __device__ __forceinline__ void stripe_sums(const u32* cs, u32 epoch, u32* err, u64 base_t,
-                                            u64 G, u64 w, bool need_all, StripeCounts& c,
-                                            u64* s_red, u64* below, u64* all) {
+                                            u64 G, u64 ntiles, u64 w, bool need_all,
+                                            StripeCounts& c, u64* s_red, u64* below, u64* all) {
   const int tid = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < CQ; q++) {  // absent tiles count 0
+    const u64 x = (u64)tid + (u64)q * JB;
+    c.v[q] = x < G && base_t + x < ntiles ? c.v[q] : epoch << CNT_BITS;
+  }
   // counts this workgroup needs: all of the stripe's (for the next stripe's base), or
   // only those of the workgroups below it (its last tile: no next stripe)
   const u64 need = need_all ? G : w;
@@ -733,11 +754,15 @@ __device__ __forceinline__ void stripe_sums(const u32* cs, u32 epoch, u32* err, 
       break;
     }
     __builtin_amdgcn_s_sleep(2);
+    // (the granules' address again from the argument segment, as grid_check reads its own:
+    // the lane's address into `cs` otherwise holds a register pair across the tile loop for
+    // this rare path, which the keyed kernels with change events spill)
+    const u32* cs_poll = cold(&cold_scan()->counts);
 #pragma unroll
     for (int q = 0; q < CQ; q++) {
       const u64 x = (u64)tid + (u64)q * JB;
       if (x < need && (c.v[q] >> CNT_BITS) != epoch)
-        c.v[q] = __hip_atomic_load(cs + base_t + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        c.v[q] = __hip_atomic_load(cs_poll + base_t + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   u64 lo = 0, tot = 0;
@@ -811,7 +836,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       int gnat, gnbt;
       u64 gb0;
       tile_geom(w, p.jt, ga0, ga1, total, &gnat, &gnbt, &gb0);
-      issue_tile(A, B, gnat, gnbt, ga0, gb0, r);
+      issue_tile(A, B, gnat, ga0, gb0, r);
     }
     // merge-path splits of this workgroup's (<= FUSE_IT) tiles: boundary q (tile q / 2,
     // side q % 2) by wave q mod the block's waves
@@ -860,10 +885,22 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   };
   u64 t = w;
   u64 a0 = split(t, 0, 0), a1 = split(t, 0, 1);
+  // The partitioned kernel reads a tile's splits from the partition's array one iteration
+  // before it issues the tile: read where they are used, their wait (a memory round trip)
+  // stood before the tile's loads.  (Not the keyed kernels: they have no registers to
+  // carry them in.)
+  constexpr bool AHEAD = !LATE && !KEYED;
+  u64 sa0 = 0, sa1 = 0;  // AHEAD: the splits of tile t + G
+  auto splits_ahead = [&](u64 tile) {  // (clamped: the array has ntiles + 1 entries)
+    const u64 tq = min(tile, ntiles - 1);
+    sa0 = p.splits[tq];
+    sa1 = p.splits[tq + 1];
+  };
+  if (AHEAD) splits_ahead(t + G);
   int nat, nbt;
   u64 b0;
   tile_geom(t, p.jt, a0, a1, total, &nat, &nbt, &b0);
-  if (!LATE || a0 != ga0 || a1 != ga1) issue_tile(A, B, nat, nbt, a0, b0, r);  // (uniform)
+  if (!LATE || a0 != ga0 || a1 != ga1) issue_tile(A, B, nat, a0, b0, r);  // (uniform)
   u64 kl = 0, km = 0, kk = 0;
   if (KEYED) {
     km = kslice(t, 0, &kl);
@@ -894,18 +931,25 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     // since the fused merge has no flat loads left (NOFB below) the early issue wins there
     // too: config 2 34.1-35.2 against 36.1-37.2 us per join, A/B on one box, three rounds.)
     auto issue_next = [&]() {
-      a0n = split(tn, k + 1, 0);
-      a1n = split(tn, k + 1, 1);
+      a0n = AHEAD ? sa0 : split(tn, k + 1, 0);
+      a1n = AHEAD ? sa1 : split(tn, k + 1, 1);
+      // (sa0 / sa1 end here, before the load that refills them: while they overlapped it the
+      // load went to other registers and was waited for at once, to be copied)
+      if (AHEAD) asm volatile("" : "+v"(a0n), "+v"(a1n) : : "memory");
       tile_geom(tn, p.jt, a0n, a1n, total, &natn, &nbtn, &b0n);
-      issue_tile(A, B, natn, nbtn, a0n, b0n, r);
+      issue_tile(A, B, natn, a0n, b0n, r);
+      if (AHEAD) splits_ahead(tn + G);
       if (KEYED) {
         kmn = kslice(tn, k + 1, &kln);
-        if (kmn <= (u64)KS && (u64)tid < kmn) kk = p.keys[kln + tid];
+        // (the slice's start as a scalar: added to the lane's index first, the compiler
+        // keeps p.keys + tid in a register pair across the loop, which the keyed kernels
+        // with change events spill)
+        const u64 kls = ((u64)__builtin_amdgcn_readfirstlane((int)(kln >> 32)) << 32) |
+                        (u32)__builtin_amdgcn_readfirstlane((int)kln);
+        if (kmn <= (u64)KS && (u64)tid < kmn) kk = (p.keys + kls)[tid];
       }
     };
     if (tn < ntiles) issue_next();
-    StripeCounts sc;  // stripe k-1's counts, in flight during the merge
-    if (k > 0) stripe_load(cs, t - G - w, G, ntiles, epoch, sc);
     JSTAMP(t, 7);
     u32 keep, ev = 0;
     unsigned short src[JI];
@@ -928,6 +972,14 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     for (int q = 0; q < JI; q++)
       if (keep & (1u << q)) s.comp[bi][pos++] = src[q];
     if (tid == 0) publish_count(cs, t, epoch, n);
+    // stripe k-1's counts: loaded here, behind this tile's own count, and in flight across
+    // the barrier.  Loaded before the merge, beside the tile loads, they were read before the stripe's slower workgroups had published, and the re-poll
+    // of stripe_sums (a sleep and a round trip per try) cost more than the overlap gave:
+    // config 2 35.9-36.9 us per join before the tile loads and 37.5-37.7 after them, against
+    // 33.0-34.0 after the merge and 33.5-33.8 here (parent 34.2-35.2; A/B on one box).
+    // (With change events they are loaded behind that block, not held across it.)
+    StripeCounts sc;
+    if (!CHG && k > 0) stripe_load(cs, t - G - w, G, ntiles, epoch, sc);
     __syncthreads();
     if (CHG) {  // the tile's change events (keys, ascending, repeats allowed) -> chg_tmp,
                 // with the per-tile figures the changed-key kernels need (chg_sum/write)
@@ -984,11 +1036,13 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       }
       if (ne && p0 == 0) p.chg_fk[t] = fkey;
       if (ne && p2 == n2) p.chg_lk[t] = lkey;
+      if (k > 0) stripe_load(cs, t - G - w, G, ntiles, epoch, sc);
     }
     JSTAMP(t, 4);
     if (k > 0) {  // stripe k-1: this workgroup's tile t - G
       u64 below, all;
-      stripe_sums(cs, epoch, p.scan.err, t - G - w, G, w, true, sc, s.red[k & 1], &below, &all);
+      stripe_sums(cs, epoch, p.scan.err, t - G - w, G, ntiles, w, true, sc, s.red[k & 1], &below,
+                  &all);
       JSTAMP(t, 5);
       write_tile(p, s, bi ^ 1, base + below, np);
       base += all;
@@ -999,7 +1053,8 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       u64 below, all;
       StripeCounts last;
       stripe_load(cs, t - w, G, ntiles, epoch, last);
-      stripe_sums(cs, epoch, p.scan.err, t - w, G, w, false, last, s.red[(k + 1) & 1], &below, &all);
+      stripe_sums(cs, epoch, p.scan.err, t - w, G, ntiles, w, false, last, s.red[(k + 1) & 1],
+                  &below, &all);
       write_tile(p, s, bi, base + below, np);
       if (tid == 0 && t == ntiles - 1) p.d_count[0] = base + below + np;
       break;
@@ -1198,7 +1253,7 @@ __global__ __launch_bounds__(JB) void join2_slot_kernel(JoinArgs p) {
   u64 b0;
   tile_geom(t, p.jt, a0, a1, total, &nat, &nbt, &b0);
   Staged r;
-  issue_tile(p.a, p.b, nat, nbt, a0, b0, r);
+  issue_tile(p.a, p.b, nat, a0, b0, r);
   __syncthreads();  // zeroed tables visible
   if (FAST) fill_vv_tables(p.ca, p.cb, s.u.tab[0], s.u.tab[1]);
   JSTAMP(t, 0);
@@ -1383,7 +1438,8 @@ hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& 
     p.chg_lk = l.lk;
   }
   if (p.ntiles == 0) {
-    // no rows: only the context union runs
+    // no rows: only the context union runs.  (No tile kernel below is launched without
+    // rows: slot_row clamps a load's index into a store that has some.)
     hipError_t e = hipMemsetAsync(d_counts, 0, sizeof(u64), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ctx_union_kernel, dim3(1), dim3(CB), 0, st, cu);
