@@ -16,7 +16,7 @@
 // the engine's stream.  With several, every engine's join kernels run on one shared
 // stream per device, ordered with the engine's own stream by events
 // (tests/test_gpu_concurrency.py).  Against other streams' and processes' kernels the
-// grid checks its own residency and aborts (join.hip, stripe_sums); the calls then re-run
+// grid checks its own residency and aborts (join_stream.hip, stripe_sums); the calls then re-run
 // on kernels that do not wait (dg_join2, dg_engine_sync, dg_join2_changes).
 struct DevShare {
   int engines = 0;

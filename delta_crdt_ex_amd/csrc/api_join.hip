@@ -22,13 +22,17 @@ int join2_enqueue(dg_engine* e, const dg_store* a, const dg_context* ca, const d
   if (a->n + b->n && (!out->key || !out->val || !out->ts || !out->node || !out->cnt))
     return fail(DG_E_INVAL, "dg_join2: null output column");
   TRY(set_device(e));
-  TRY(ensure_state(e, 3 * join2_tiles_cap(a->n, b->n) + 3));  // granules + tile + keyset splits
+  const u64 tiles = join2_tiles(a->n, b->n), tiles_cap = join2_tiles_cap(a->n, b->n);
+  Arena state;  // (measured: launch_join2 carves it)
+  join_state_layout(state, tiles_cap);
+  TRY(ensure_state(e, state.off / sizeof(u64)));
   const bool two_pass = (force_two_pass || e->join_mode == JOIN_TWO_PASS) && !chg;  // changes: single pass
-  if (!two_pass) TRY(ensure_counts(e, join2_tiles_cap(a->n, b->n)));
+  if (!two_pass) TRY(ensure_counts(e, tiles_cap));
   JoinScratch js;
   TRY(carve(e, &e->tmp, [&](Arena& m) {
-    return join_layout(m, ctx_union_tmp_bytes(ca->n, cb->n), two_pass ? join2_pass_tmp_bytes(a->n, b->n) : 0,
-                       chg ? join2_changes_tmp_bytes(a->n, b->n) : 0);
+    return join_layout(m, ctx_union_tmp_bytes(ca->n, cb->n),
+                       two_pass ? measured([&](Arena& x) { pass_layout(x, tiles, JOIN_TILE); }) : 0,
+                       chg ? measured([&](Arena& x) { chg_layout(x, tiles, JOIN_TILE); }) : 0);
   }, &js));
   if (chg) *chg = js.chg;
   Scan sc;

@@ -4,6 +4,7 @@
 // and runs it again on the buffer: the size and the pointers come from the same lines
 // (tests/arena_layouts.cc checks every layout against its offsets and under ASan).
 #pragma once
+#include <cassert>
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
@@ -63,6 +64,76 @@ inline JoinScratch join_layout(Arena& a, size_t ctx_bytes, size_t pass_bytes, si
   s.ctx = a.take<char>(ctx_bytes);
   s.pass = a.take<char>(pass_bytes);
   s.chg = chg_bytes ? a.take<char>(chg_bytes) : nullptr;
+  return s;
+}
+
+// The bytes a layout asks for: what its caller passes on as a region of another layout.
+template <class Layout>
+size_t measured(Layout layout) {
+  Arena m;
+  layout(m);
+  return m.bytes();
+}
+
+// The three scratch layouts below are carved by the join's launchers (join*.hip) and
+// measured by join2_enqueue; `tile` is JOIN_TILE (this header knows no kernel constant).
+
+// The join's share of the engine's u64 state words (Scan::state; sized for the tiles after
+// a re-cut, join2_tiles_cap, carved for the tiles in use): ntiles words no join kernel
+// touches (the look-back granules of the kernel before the stripe counts; they keep the
+// splits where they were) | the merge-path split of every tile boundary (ntiles + 1) | the
+// keyset splits (ntiles + 1)
+struct JoinState {
+  uint64_t *splits, *ksplits;
+};
+inline JoinState join_state_layout(Arena& a, uint64_t ntiles) {
+  JoinState s;
+  a.take<uint64_t>(ntiles, 8);
+  s.splits = a.take<uint64_t>(ntiles + 1, 8);
+  s.ksplits = a.take<uint64_t>(ntiles + 1, 8);
+  return s;
+}
+
+// The two-pass join (join_layout's pass): kept rows per tile | per tile its compaction
+// list, `tile` u16 LDS slot numbers
+struct PassScratch {
+  uint32_t* counts;
+  unsigned short* lists;
+};
+inline PassScratch pass_layout(Arena& a, uint64_t ntiles, uint64_t tile) {
+  PassScratch s;
+  s.counts = a.take<uint32_t>(ntiles);
+  s.lists = a.take<unsigned short>(ntiles * tile);
+  return s;
+}
+
+// The change events (join_layout's chg): per tile `tile` event keys | the chunk summaries
+// (ntiles x 8 bytes) | per tile its event count, its events that differ from their
+// predecessor, and a third u32 nothing uses (it keeps the offsets behind it) | per tile
+// its first and its last event.  A chunk summary (join_changes.hip ChgSum) covers
+// CHG_CHUNK tiles; the last chunk's is never written, so ceil(ntiles / CHG_CHUNK) - 1 of
+// them must fit their region.
+constexpr uint64_t CHG_CHUNK = 64;
+constexpr size_t CHG_SUM_BYTES = 32;
+struct ChgScratch {
+  uint64_t* ev;
+  void* chunk;
+  uint32_t *cnt, *wu;
+  uint64_t *fk, *lk;
+};
+inline ChgScratch chg_layout(Arena& a, uint64_t ntiles, uint64_t tile) {
+  ChgScratch s;
+  s.ev = a.take<uint64_t>(ntiles * tile, 8);
+  s.chunk = a.take<char>(ntiles * 8, 8);
+  const uint64_t chunks = (ntiles + CHG_CHUNK - 1) / CHG_CHUNK;
+  assert(chunks <= 1 || (chunks - 1) * CHG_SUM_BYTES <= ntiles * 8);
+  (void)chunks;
+  s.cnt = a.take<uint32_t>(ntiles, 4);
+  s.wu = a.take<uint32_t>(ntiles, 4);
+  a.take<uint32_t>(ntiles, 4);
+  a.align_to(8);
+  s.fk = a.take<uint64_t>(ntiles, 8);
+  s.lk = a.take<uint64_t>(ntiles, 8);
   return s;
 }
 

@@ -99,11 +99,11 @@ struct dg_engine {
 // e->ticket[0..16)
 enum Ticket {
   TK_TILE = 0,    // the look-back kernels' tile ticket (join, take, kfold: left at 0 by every launch)
-  TK_ERR = 1,     // error bits: a look-back timeout, an aborted join grid (join.hip)
+  TK_ERR = 1,     // error bits: a look-back timeout, an aborted join grid (join_stream.hip)
   TK_ORDER = 2,   // dg_store_check's flag (store_check_kernel)
   TK_INPUT = 3,   // a call's input-error word: the Merkle build / update (MERKLE_INPUT_ERR), the
                   // mutation count (unsorted ops), remap and mark (bad ids)
-  TK_ABORT = 4,   // the join abort epoch (join.hip, stripe_sums)
+  TK_ABORT = 4,   // the join abort epoch (join_stream.hip, stripe_sums)
   TK_UNUSED = 5,
   // The Merkle kernels' arrival counter.  It is reset by the last workgroup of every build /
   // update launch, not per launch.  A launch either runs every workgroup to that reset (the
@@ -121,7 +121,7 @@ constexpr int CONT_HOME = 18;  // h_pub words [18, 24): dg_merkle_continue_home'
 
 // e->d_counts[0..8) (and their mirror e->h_counts), by the path that is running
 enum JoinCount {    // the join kernels, and the splice around them
-  JC_ROWS = 0,      // output rows (join.hip; take, read, sort, the Merkle calls: their one count)
+  JC_ROWS = 0,      // output rows (the join kernels; take, read, sort, the Merkle calls: their one count)
   JC_CTX = 1,       // the union context's entries (ctx_union_block)
   JC_CHANGED = 2,   // changed keys (launch_join2_changes)
   SC_TAKEN = 3,     // the state's rows of the keyset (take.hip)

@@ -8,11 +8,13 @@
 
 namespace dg {
 
-// Per-launch scratch for single-pass compaction kernels (decoupled look-back).
+// Per-launch scratch of the single-pass compaction kernels.  take.hip and kfold.hip resolve
+// their output offsets by decoupled look-back over `state`; the join keeps its splits in
+// `state` (join_state_layout) and counts its tiles in `counts`.
 struct Scan {
-  u64* state;   // one granule per tile (device)
+  u64* state;   // u64 words (device): one look-back granule per tile, or the join's splits
   u32* ticket;  // tile ticket counter, left at 0 by every launch (device)
-  u32* err;     // error bits (device): 1 = look-back timeout
+  u32* err;     // error bits (device): 1 = a wait timed out, 2 = the join grid aborted
   u32 epoch;    // granules of other epochs are ignored
   u32* counts;  // per-tile count granules {epoch:20 | count:12} of the single-pass join
                 // (written only by that kernel, zeroed when allocated)
@@ -24,9 +26,9 @@ struct Scan {
   u32* abort;
 };
 
-constexpr u64 JOIN_MAX_GRID = 2048;  // >= every single-pass join grid (join.hip checks)
+constexpr u64 JOIN_MAX_GRID = 2048;  // >= every single-pass join grid (dg_jtile.h checks)
 
-// ---- join.hip
+// ---- join.hip, join_stream.hip, join_twopass.hip, join_changes.hip (dg_jtile.h maps them)
 #ifndef DG_JOIN_BLOCK
 #define DG_JOIN_BLOCK 512
 #endif
@@ -43,32 +45,25 @@ inline u64 join2_tiles(u64 na, u64 nb) { return (na + nb + JOIN_TILE - 1) / JOIN
 // tiles of a join after launch_join2 re-cuts them to fill its grid's stripes (fewer than
 // one more per workgroup): what the split and tile-count scratch is sized for
 inline u64 join2_tiles_cap(u64 na, u64 nb) { return join2_tiles(na, nb) + JOIN_MAX_GRID; }
-// join/3: a merge-path partition pass (its extra workgroup computes the context union,
-// d_counts[1] = its size), then one workgroup per tile that merges it, resolves its
-// output offset by decoupled look-back and writes its kept rows (d_counts[0] = output
-// rows).  Uses scan.state[0, 2 * ntiles + 2).  JOIN_TWO_PASS replaces the look-back by
-// a count/compact pass pair (pass_tmp: join2_pass_tmp_bytes) whose first pass runs
-// `workers` persistent workgroups.
+// join/3 (d_counts[0] = output rows, d_counts[1] = the union context's entries): a grid of
+// resident workgroups (`workers` of them; 0: as many as the device holds) streams the
+// tiles, each summing the tile counts before its own in scan.counts.  The tile boundaries'
+// merge-path splits come from a partition launch, whose extra workgroup computes the
+// context union; a join of few tiles per workgroup is one launch that does all three.
+// scan.state holds the splits (join_state_layout at join2_tiles_cap).  JOIN_TWO_PASS: a
+// count and a compact pass behind the partition instead, one workgroup per tile, none
+// waiting on another (pass_tmp: pass_layout; ignored otherwise).
 enum { JOIN_SINGLE_PASS = 0, JOIN_TWO_PASS = 1 };
 hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& cb,
                         const u64* keys, u64 n_keys, const RowsOut& out, u32* out_ctx_node,
                         u64* out_ctx_cnt, void* ctx_tmp, void* pass_tmp, int mode,
                         const Scan& scan, int workers, u64* d_counts, hipStream_t st,
                         void* chg_tmp = nullptr);
-// Changed keys (dg_join2_changes): with chg_tmp (join2_changes_tmp_bytes) the join
+// Changed keys (dg_join2_changes): with chg_tmp (chg_layout at join2_tiles) the join
 // records per-tile change events (always the single-pass kernel); launch_join2_changes
 // then drops repeats and compacts them into out[0, cap) (*d_count = changed keys).
-// chg_tmp: JOIN_TILE u64 events + u64 offset + 3 u32 + first/last event (2 u64) per tile.
-inline size_t join2_changes_tmp_bytes(u64 na, u64 nb) {
-  const u64 t = join2_tiles(na, nb);
-  return t * ((u64)JOIN_TILE * 8 + 8 + 12 + 16) + 8 + 256;
-}
 hipError_t launch_join2_changes(u64 na, u64 nb, void* chg_tmp, u64* out, u64 cap, u64* d_count,
                                 hipStream_t st);
-inline size_t join2_pass_tmp_bytes(u64 na, u64 nb) {
-  const u64 t = join2_tiles(na, nb);
-  return ((t * 4 + 255) / 256) * 256 + t * (u64)JOIN_TILE * 2 + 256;  // counts + slot lists
-}
 // Dots.union/2 of two contexts; out kind: DOTS iff both DOTS.  Writes |out| to *d_count.
 // tmp: (a.n + b.n) u32 + (a.n + b.n) u64 + (a.n + b.n + 1) u32 of device scratch.
 hipError_t launch_ctx_union(const Ctx& a, const Ctx& b, u32* out_node, u64* out_cnt,

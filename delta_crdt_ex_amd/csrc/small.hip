@@ -168,7 +168,7 @@ __device__ __forceinline__ void block_scan4(const u32 (&v)[4], u32* sw, u32 (&ex
 }
 
 // Map.get(vv, n, 0) >= c for a VV table of counter + 1 (0: absent, which covers cnt 0 as
-// the reference's Dots.member? does, aw_lww_map.ex:67-70, and the fused join, join.hip)
+// the reference's Dots.member? does, aw_lww_map.ex:67-70, and the fused join, dg_jtile.h)
 __device__ __forceinline__ bool vv_tab_covers(const u64* tab, u32 n, u64 c) {
   return n < SV ? max(tab[n], 1ull) > c : c == 0;
 }

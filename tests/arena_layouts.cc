@@ -106,6 +106,52 @@ static void test_join() {
         });
 }
 
+// The three layouts the join's launchers carve (join*.hip) and join2_enqueue measures: the
+// old offsets are launch_join2's place_splits and pass carve, join.hip's chg_layout, and the
+// byte formulas of dg_launch.h (join2_pass_tmp_bytes, join2_changes_tmp_bytes) and
+// api_join.hip (3 * tiles + 3 state words).
+static const u64 JOIN_TILES[] = {0, 1, 63, 64, 65, 129, 4096};
+static const u64 JT = 1016, JOIN_MAX_GRID = 2048;  // JOIN_TILE; join2_tiles_cap's margin
+
+static void test_join_state() {
+  for (u64 t : JOIN_TILES)
+    for (u64 n : {t, t + JOIN_MAX_GRID})
+      run("join state", (3 * n + 3) * 8, [&](Arena& a, std::vector<Region>& r) {
+        JoinState s = join_state_layout(a, n);
+        r.push_back({"splits", s.splits, (n + 1) * 8, 8, 8, n * 8});
+        r.push_back({"ksplits", s.ksplits, (n + 1) * 8, 8, 8, (2 * n + 1) * 8});
+        CHECK(a.off == (3 * n + 2) * 8, "join state: %zu bytes for %llu tiles", a.off, (unsigned long long)n);
+      });
+}
+
+static void test_pass() {
+  for (u64 n : JOIN_TILES)
+    run("pass", (n * 4 + 255) / 256 * 256 + n * JT * 2 + 256, [&](Arena& a, std::vector<Region>& r) {
+      PassScratch s = pass_layout(a, n, JT);
+      r.push_back({"counts", s.counts, n * 4, 4, 4, 0});
+      r.push_back({"lists", s.lists, n * JT * 2, 2, 2, (n * 4 + 255) / 256 * 256});
+    });
+}
+
+static void test_chg() {
+  for (u64 n : JOIN_TILES)
+    run("chg", n * (JT * 8 + 8 + 12 + 16) + 8 + 256, [&](Arena& a, std::vector<Region>& r) {
+      ChgScratch s = chg_layout(a, n, JT);
+      const size_t off = n * JT * 8, cnt = off + n * 8, fk = (cnt + 3 * n * 4 + 7) / 8 * 8;
+      r.push_back({"ev", s.ev, n * JT * 8, 8, 8, 0});
+      r.push_back({"chunk", s.chunk, n * 8, 8, 8, off});
+      r.push_back({"cnt", s.cnt, n * 4, 4, 4, cnt});
+      r.push_back({"wu", s.wu, n * 4, 4, 4, cnt + n * 4});
+      r.push_back({"fk", s.fk, n * 8, 8, 8, fk});
+      r.push_back({"lk", s.lk, n * 8, 8, 8, fk + n * 8});
+      // the chunk summaries written: one of 32 bytes per 64 tiles, but the last
+      const u64 written = n ? (n + 63) / 64 - 1 : 0;
+      CHECK(CHG_CHUNK == 64 && CHG_SUM_BYTES == 32, "chg: chunk constants");
+      const size_t room = a.base ? (size_t)((const char*)s.cnt - (const char*)s.chunk) : n * 8;
+      CHECK(written * 32 <= room, "chg: %llu summaries in %zu bytes", (unsigned long long)written, room);
+    });
+}
+
 static void test_splice() {
   for (u64 rows : SIZES)
     for (u64 nk : SIZES)
@@ -297,6 +343,9 @@ static void test_mark() {
 int main() {
   test_context();
   test_join();
+  test_join_state();
+  test_pass();
+  test_chg();
   test_splice();
   test_kd();
   test_home();

@@ -7,7 +7,7 @@ partitioned one behind join2_partition_kernel -- or the two-pass pair join2_slot
 join2_compact_kernel; the fused kernel also picks one of two merge bodies from its VVs' node
 ids.  From outside the library only the joined rows show, so WHICH of them a call runs is
 decided here, by a restatement of the host's decisions.  tests/test_join_routes.py pins the
-constants below to csrc/dg_launch.h and csrc/join.hip and the model's answer for every
+constants below to csrc/dg_launch.h and the units of the join and the model's answer for every
 (engine, shape) pair of the GPU file, whose tests assert through route() that each call
 lands where it is meant to.
 
@@ -28,7 +28,7 @@ TOP = (1 << 64) - 1
 
 # ---------------------------------------------------------------- the constants (one table)
 # csrc/dg_launch.h: DG_JOIN_BLOCK, DG_JOIN_ITEMS, JOIN_TILE = block * items - JOIN_TILE_LESS;
-# csrc/join.hip: FUSE_IT, VT, KS, CQ = ceil(CQ_SPAN / block); csrc/api_join.hip: splice_wanted's
+# csrc/dg_jtile.h: FUSE_IT, VT, KS, CQ = ceil(CQ_SPAN / block); csrc/api_join.hip: splice_wanted's
 # factor.  (test_join_routes.py::test_constants_match_the_sources)
 CONST = {"DG_JOIN_BLOCK": 512, "DG_JOIN_ITEMS": 2, "JOIN_TILE_LESS": 8, "FUSE_IT": 4, "VT": 64,
          "KS": 64, "CQ_SPAN": 1024, "SPLICE_FACTOR": 8}

@@ -3,7 +3,7 @@ fallbacks only such key sets reach (helper module: no tests).
 
 Every workload generator draws key ids as 64-bit hashes, and the device searches are tuned
 for that: interp_lower_bound (csrc/dg_device.h) brackets a uniform key in its six
-interpolation rounds, mp_split (csrc/join.hip) in its first 64-wide window.  The key sets
+interpolation rounds, mp_split (csrc/dg_jsplit.h) in its first 64-wide window.  The key sets
 here send them to their exact fallbacks (the plain binary search, mp_search's 128-ary
 search); the models count which exit a lookup takes, so tests/test_skew_models.py can
 assert that the inputs of tests/test_gpu_skewed_keys.py do reach those exits."""
@@ -220,12 +220,12 @@ WAVE, PK = 64, 128
 
 
 def _mp_pred(A, B, d, i):
-    # mp_pred of csrc/join.hip for disjoint key sets: the keys never tie, so no full row is read
+    # mp_pred of csrc/dg_jsplit.h for disjoint key sets: the keys never tie, so no full row is read
     return A[i] < B[d - 1 - i]
 
 
 def _model_mp_search(A, B, d, lo, hi):
-    """mp_search of csrc/join.hip: first i in [lo, hi) with NOT mp_pred(i), 128-ary."""
+    """mp_search of csrc/dg_jsplit.h: first i in [lo, hi) with NOT mp_pred(i), 128-ary."""
     for _ in range(64):
         if not hi > lo:
             break
@@ -250,7 +250,7 @@ def _model_mp_search(A, B, d, lo, hi):
 
 
 def model_mp_split(A_keys, B_keys, d):
-    """mp_split of csrc/join.hip, line by line, for two stores whose key sets are disjoint
+    """mp_split of csrc/dg_jsplit.h, line by line, for two stores whose key sets are disjoint
     (only keys are compared).  A_keys, B_keys: the stores' key columns.  Returns
     (split, path): `short` (a diagonal of at most 128 candidates: mp_search at once),
     `win0` / `win1` / `win2` (bracketed by that 64-wide window) or `search` (three windows

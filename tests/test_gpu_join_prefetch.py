@@ -1,5 +1,6 @@
 """The stream kernel's tile loader, commit and stripe counts at the shapes where they can go
-wrong (csrc/join.hip: slot_row, issue_tile, commit_tile, stripe_load).  Every lane loads a
+wrong (csrc/dg_jtile.h: slot_row, issue_tile, commit_tile; csrc/join_stream.hip:
+stripe_load).  Every lane loads a
 row for every staging slot, at an index clamped into a store that has rows, and commits it,
 so a slot without a row holds a copy of a real one that the merge must not use.  The shapes
 are those where slots have no row or a store has none: an empty side (null columns), one

@@ -1,4 +1,5 @@
-"""The join kernels no other test selects (csrc/join.hip): node ids of VT = 64 and above in
+"""The join kernels no other test selects (csrc/join.hip, join_stream.hip,
+join_twopass.hip): node ids of VT = 64 and above in
 rows and version vectors -- the fused kernel's two merge bodies and the searching coverage
 of the partitioned and two-pass kernels -- and small grids: four fused iterations per
 workgroup, the partitioned stream kernel on one and two workgroups, and the two-pass

@@ -1,5 +1,5 @@
 """The CPU model of launch_join2's choice of kernels (tests/join_routes.py): pinned to the
-constants and the decisions of csrc/dg_launch.h, csrc/join.hip and csrc/api_join.hip, and
+constants and the decisions of csrc/dg_launch.h, the join's units and csrc/api_join.hip, and
 -- for every (engine, shape) pair tests/test_gpu_join_variants.py joins -- the model's
 answer pinned here, so a retune of the tile, of FUSE_IT or of the grid's bound fails a test
 instead of silently moving the GPU cases off the kernels they are for.  Also the
@@ -20,12 +20,18 @@ def _src(name):
     return open(os.path.join(CSRC, name)).read()
 
 
+# the join's kernels and launchers: launch_join2 and the partition (join.hip), the stream
+# kernel, the two-pass pair, and the two headers they share
+JOIN_UNITS = ("join.hip", "join_stream.hip", "join_twopass.hip", "dg_jtile.h", "dg_jsplit.h")
+
+
 # ---------------------------------------------------------------- the model is the sources'
 
 def test_constants_match_the_sources():
-    """join_routes.CONST restates csrc/dg_launch.h and csrc/join.hip: if the tile, FUSE_IT,
-    VT, KS or the grid's bound moves there, the model is wrong until it follows."""
-    h, j, api = _src("dg_launch.h"), _src("join.hip"), _src("api_join.hip")
+    """join_routes.CONST restates csrc/dg_launch.h and the join's units (JOIN_UNITS): if the
+    tile, FUSE_IT, VT, KS or the grid's bound moves there, the model is wrong until it
+    follows."""
+    h, j, api = _src("dg_launch.h"), "\n".join(_src(u) for u in JOIN_UNITS), _src("api_join.hip")
     got = {}
     for name in ("DG_JOIN_BLOCK", "DG_JOIN_ITEMS"):
         got[name] = int(re.search(r"#define\s+%s\s+(\d+)" % name, h).group(1))
