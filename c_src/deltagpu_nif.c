@@ -43,6 +43,7 @@
  *        (dg_join_deltas); changed and diffs are NET over the batch
  *   read(state, version, keys | :all)                 -> {:ok, %{key => value}}  (:211-224)
  *   take(state, version, keys)                         -> {:ok, value map}  (Map.take, :118,331)
+ *   take_batch(state, version, [keys, ...])            -> {:ok, [value map, ...]}  (k takes, one pass)
  *   merkle_build(state, version, depth)                -> :ok
  *   merkle_prepare(state, version, levels)             -> {:continue, cont}     (:255)
  *   merkle_continue(state, version, cont, levels, max) -> {:continue, cont} | {:ok, keys}
@@ -1003,6 +1004,62 @@ out:
   return r;
 }
 
+/* take_batch(state, version, [keys, ...]) -> {:ok, [value map, ...]}: take/3 for k pending
+ * get_diff / send_diff messages, one dgr_take_batch per 64 keysets.  Every row of the keysets'
+ * union comes home and becomes terms ONCE; the messages that hold a key share its value map. */
+#define TAKE_BATCH_MAX 64
+static ERL_NIF_TERM take_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  state_res* s;
+  uint64_t version;
+  unsigned total;
+  if (!get_state(env, argv[0], argv[1], &s, &version) || !enif_get_list_length(env, argv[2], &total))
+    return enif_make_badarg(env);
+  engine_res* g = s->eng;
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  uint64_t* keys[TAKE_BATCH_MAX];
+  uint64_t n_keys[TAKE_BATCH_MAX];
+  memset(keys, 0, sizeof keys);
+  ERL_NIF_TERM* maps = (ERL_NIF_TERM*)enif_alloc((total ? total : 1) * sizeof *maps);
+  ERL_NIF_TERM r, h, t = argv[2];
+  unsigned done = 0;
+  if (!maps) TRY(DG_E_NOMEM);
+  while (done < total) {
+    int k = 0;
+    while (k < TAKE_BATCH_MAX && enif_get_list_cell(env, t, &h, &t)) {
+      TRY(marshal_keys(env, g, h, &keys[k], &n_keys[k]));
+      k++;
+    }
+    if (k == 0) TRY(DG_E_INVAL);
+    dgr_taken tk;
+    ERL_NIF_TERM values;
+    TRY(dgr_take_batch(s->s, version, k, (const uint64_t* const*)keys, n_keys, &tk));
+    TRY(unmarshal_host_rows(env, g, &tk.rows, &values));
+    for (int j = 0; j < k; j++) maps[done + j] = enif_make_new_map(env);
+    for (uint64_t i = 0; i < tk.n_keys; i++) {
+      if (tk.offs[i + 1] == tk.offs[i]) continue; /* the state lacks the key */
+      const ERL_NIF_TERM kt = key_term(env, g, tk.keys[i]);
+      ERL_NIF_TERM ents;
+      if (!enif_get_map_value(env, values, kt, &ents)) TRY(DG_E_INVAL);
+      for (int j = 0; j < k; j++)
+        if (tk.masks[i] >> j & 1) enif_make_map_put(env, maps[done + j], kt, ents, &maps[done + j]);
+    }
+    for (int j = 0; j < k; j++) {
+      enif_free(keys[j]);
+      keys[j] = NULL;
+    }
+    done += (unsigned)k;
+  }
+out:
+  r = rc ? error_term(env, rc) : enif_make_tuple2(env, A_OK, enif_make_list_from_array(env, maps, total));
+  for (int j = 0; j < TAKE_BATCH_MAX; j++)
+    if (keys[j]) enif_free(keys[j]);
+  if (maps) enif_free(maps);
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
 /* merkle_build(state, version, depth) -> :ok  (MerkleMap.new + put of every key, :21) */
 static ERL_NIF_TERM merkle_build_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   (void)argc;
@@ -1176,6 +1233,7 @@ static ErlNifFunc funcs[] = {
     {"join_deltas_diffs", 3, join_deltas_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"read", 3, read_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"take", 3, take_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"take_batch", 3, take_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_build", 3, merkle_build_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_prepare", 3, merkle_prepare_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_continue", 5, merkle_continue_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},

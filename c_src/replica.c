@@ -65,6 +65,9 @@ struct dgr_engine {
   dg_store tk;
   uint64_t* h_tk;
   uint64_t h_tk_cap;
+  /* dgr_take_batch: union keys [0, K) | masks [K, 2K) | offsets [2K, 3K + 1), K = tb_cap */
+  uint64_t *d_tb, *h_tb;
+  uint64_t tb_cap;
   /* continuations: the output (device), the keys, and the bytes handed back */
   dg_merkle_cont co;
   uint64_t *d_ckeys, *h_ckeys, *h_cstage;
@@ -310,6 +313,34 @@ uint64_t dgr_batch_pack(uint64_t* host, uint64_t* dev, int k, const dg_store* de
   return o;
 }
 
+/* The packed message of k keysets (dgr_take_batch): keyset i sorted and unique at the even
+ * word offset Σ_{j<i} even(n_keys[j]).  Host code only. */
+uint64_t dgr_takes_words(int k, const uint64_t* n_keys) {
+  uint64_t w = 0;
+  for (int i = 0; i < k; i++) w += even(n_keys[i]);
+  return w;
+}
+
+uint64_t dgr_takes_pack(uint64_t* host, uint64_t* dev, int k, const uint64_t* const* keys, const uint64_t* n_keys,
+                        const uint64_t** keys_v, uint64_t* n_keys_v) {
+  uint64_t o = 0;
+  for (int i = 0; i < k; i++) {
+    /* a Merkle conversation names its keys in ascending id order: such a keyset is copied
+     * (one pass), any other sorted */
+    uint64_t j = 1;
+    while (j < n_keys[i] && keys[i][j - 1] < keys[i][j]) j++;
+    if (j >= n_keys[i]) {
+      if (n_keys[i]) memcpy(host + o, keys[i], n_keys[i] * 8);
+      n_keys_v[i] = n_keys[i];
+    } else {
+      n_keys_v[i] = sort_unique(keys[i], n_keys[i], host + o);
+    }
+    keys_v[i] = dev + o;
+    o += even(n_keys[i]);
+  }
+  return o;
+}
+
 /* ------------------------------------------------------------ engine */
 int dgr_engine_open(int device, dgr_engine** out) {
   if (!out) return DG_E_INVAL;
@@ -348,6 +379,8 @@ int dgr_engine_close(dgr_engine* g) {
   dg_host_free(e, g->h_rd);
   dg_store_free(e, &g->tk);
   dg_host_free(e, g->h_tk);
+  dg_buffer_free(e, g->d_tb);
+  dg_host_free(e, g->h_tb);
   dg_buffer_free(e, g->co.pos);
   dg_buffer_free(e, g->co.hash);
   dg_buffer_free(e, g->co.bucket);
@@ -971,6 +1004,71 @@ int dgr_take(dgr_state* s, uint64_t version, const uint64_t* keys, uint64_t n_ke
   dg_store hv = {h, h + w, (int64_t*)(h + 2 * w), (uint32_t*)(h + 4 * w), h + 3 * w, 0, umax(n, 1)};
   TRY(dg_store_download(g->e, &g->tk, &hv));
   *out = hv;
+  return DG_OK;
+}
+
+/* dgr_take_batch's key arrays for K union keys (contents not kept) */
+static int grow_taken(dgr_engine* g, uint64_t K) {
+  if (g->d_tb && g->tb_cap >= K) return DG_OK;
+  K = umax(K, 2 * g->tb_cap) + 64;
+  TRY(dg_buffer_free(g->e, g->d_tb));
+  TRY(dg_host_free(g->e, g->h_tb));
+  g->d_tb = g->h_tb = NULL;
+  g->tb_cap = 0;
+  TRY(dg_buffer_alloc(g->e, (3 * K + 1) * 8, (void**)&g->d_tb));
+  TRY(dg_host_alloc(g->e, (3 * K + 1) * 8, (void**)&g->h_tb));
+  g->tb_cap = K;
+  return DG_OK;
+}
+
+int dgr_take_batch(dgr_state* s, uint64_t version, int k, const uint64_t* const* keys, const uint64_t* n_keys,
+                   dgr_taken* out) {
+  if (!s || !out || k < 0 || k > 64 || (k && (!keys || !n_keys))) return DG_E_INVAL;
+  for (int i = 0; i < k; i++)
+    if (n_keys[i] && !keys[i]) return DG_E_INVAL;
+  TRY(check_version(s, version));
+  dgr_engine* g = s->g;
+  /* ONE message and one copy: the k keysets, each sorted and unique */
+  TRY(grow_batch(g, (uint64_t)k));
+  const uint64_t words = dgr_takes_words(k, n_keys);
+  TRY(grow_msg(g, words + 2));
+  dgr_takes_pack(g->h_msg, g->d_msg, k, keys, n_keys, g->b_keys, g->b_nk);
+  if (words) TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, words * 8));
+  uint64_t m = 0;
+  for (int i = 0; i < k; i++) m += g->b_nk[i];
+  TRY(grow_taken(g, m));
+  const uint64_t K = g->tb_cap;
+  uint64_t nu = 0;
+  uint64_t cap = umin(s->rows.n, 4 * m + 64);
+  for (int attempt = 0;; attempt++) {
+    TRY(grow_store(g, &g->tk, umax(cap, 1)));
+    g->tk.n = 0;
+    const int rc = dg_take_keysets(g->e, &s->rows, k, g->b_keys, g->b_nk, g->d_tb, g->d_tb + K, g->d_tb + 2 * K, K,
+                                   &nu, &g->tk);
+    if (rc == DG_E_CAPACITY && attempt == 0 && nu <= K) {
+      cap = g->tk.n;
+      continue;
+    }
+    TRY(rc);
+    break;
+  }
+  /* home: the union keys, their masks and offsets, then the rows -- each once */
+  if (nu) {
+    TRY(dg_copy_async(g->e, g->h_tb, g->d_tb, nu * 8));
+    TRY(dg_copy_async(g->e, g->h_tb + K, g->d_tb + K, nu * 8));
+  }
+  TRY(dg_copy_async(g->e, g->h_tb + 2 * K, g->d_tb + 2 * K, (nu + 1) * 8));
+  const uint64_t n = g->tk.n, w = even(n);
+  TRY(grow_host(g, &g->h_tk, &g->h_tk_cap, rows_words(n) + 2));
+  uint64_t* h = g->h_tk;
+  dg_store hv = {h, h + w, (int64_t*)(h + 2 * w), (uint32_t*)(h + 4 * w), h + 3 * w, 0, umax(n, 1)};
+  TRY(dg_store_download(g->e, &g->tk, &hv));
+  TRY(dg_engine_sync(g->e));
+  out->n_keys = nu;
+  out->keys = g->h_tb;
+  out->masks = g->h_tb + K;
+  out->offs = g->h_tb + 2 * K;
+  out->rows = hv;
   return DG_OK;
 }
 

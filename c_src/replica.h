@@ -180,6 +180,36 @@ int dgr_read(dgr_state* s, uint64_t version, int all, const uint64_t* keys, uint
 /* Map.take(value, keys) (causal_crdt.ex:118,331): the rows of those keys (host view). */
 int dgr_take(dgr_state* s, uint64_t version, const uint64_t* keys, uint64_t n_keys, dg_store* out);
 
+/* Map.take(value, keys_j) for k pending {:get_diff, diff, keys} / send_diff messages as one
+ * call: the k keysets (host ids, any order, duplicates allowed, as for dgr_take) go down as ONE
+ * packed message and one copy, dg_take_keysets locates every distinct key once and takes its
+ * rows once, and the union keys, their masks (bit j: keyset j holds the key), offsets and rows
+ * come home once, as host views into engine-owned buffers (valid until the next call on the
+ * engine).  Message j's rows are the ranges rows[offs[i], offs[i + 1]) of the keys i whose
+ * mask has bit j, in that order; offs[n_keys] == rows.n.  Versions as for dgr_take:
+ * DGR_E_STALE for an older struct, and the version does not move on.  k > 64: DG_E_INVAL
+ * (the term layers chunk by 64); k == 0: no key, no row. */
+typedef struct dgr_taken {
+  uint64_t n_keys;
+  const uint64_t* keys;
+  const uint64_t* masks;
+  const uint64_t* offs;
+  dg_store rows;
+} dgr_taken;
+int dgr_take_batch(dgr_state* s, uint64_t version, int k, const uint64_t* const* keys, const uint64_t* n_keys,
+                   dgr_taken* out);
+
+/* Its packed message, host code only (the host test c_src/test_takes.c checks them).
+ * dgr_takes_words: its length in 8-byte words.  dgr_takes_pack: keyset i sorted and unique
+ * (n_keys_v[i] entries) written to `host` at the word offset Σ_{j<i} of the even numbers of
+ * words >= n_keys[j] (16-byte aligned); keys_v[i]: the same place in `dev`, the message's
+ * device copy.  A keyset given ascending and unique (the order in which a Merkle conversation
+ * names its keys) is copied in one pass instead of sorted.  Returns the words written,
+ * dgr_takes_words' figure. */
+uint64_t dgr_takes_words(int k, const uint64_t* n_keys);
+uint64_t dgr_takes_pack(uint64_t* host, uint64_t* dev, int k, const uint64_t* const* keys, const uint64_t* n_keys,
+                        const uint64_t** keys_v, uint64_t* n_keys_v);
+
 /* MerkleMap.new + put of every key (causal_crdt.ex:21): the state's tree, rows hashed
  * through the engine's term tables (refresh them first).  Rebuilding replaces it. */
 int dgr_merkle_build(dgr_state* s, uint64_t version, uint32_t depth);

@@ -358,4 +358,26 @@ inline MarkScratch mark_layout(Arena& a, uint64_t n_stores, size_t seg_bytes, ui
   return s;
 }
 
+// dg_take_keysets (engine tmp): the keyset descriptors (k + 1, staged in pinned memory first)
+// | the m items end to end and their set numbers | the union keys | the take's per-key
+// first rows and offsets (m + 1) | the sort's scratch
+struct TakesetsScratch {
+  void* segs;
+  uint64_t* cat;
+  uint8_t* set;
+  uint64_t *ukeys, *key_lo, *key_off;
+  void* sort_tmp;
+};
+inline TakesetsScratch takesets_layout(Arena& a, uint64_t k, size_t seg_bytes, uint64_t m, size_t sort_bytes) {
+  TakesetsScratch s;
+  s.segs = a.take<char>((k + 1) * seg_bytes);
+  s.cat = a.take<uint64_t>(m);
+  s.set = a.take<uint8_t>(m);
+  s.ukeys = a.take<uint64_t>(m);
+  s.key_lo = a.take<uint64_t>(m);
+  s.key_off = a.take<uint64_t>(m + 1);
+  s.sort_tmp = a.take<char>(sort_bytes);
+  return s;
+}
+
 }  // namespace dg

@@ -152,6 +152,29 @@ hipError_t launch_take_keys(const Rows& s, const u64* keys, u64 n_keys, const Ro
                             u64* key_lo = nullptr, u64* key_off = nullptr,
                             const u32* pre_len = nullptr);
 
+// ---- takesets.hip (k keysets -> their union with per-key set masks; see the file header)
+constexpr int KS_MAX_K = 64;     // keysets per call (masks are u64)
+constexpr int KS_BLOCK = 256;    // threads of a gather / union workgroup
+constexpr int KS_ITEMS = 4;      // sorted items per thread of the union kernel
+constexpr int KS_TILE = KS_BLOCK * KS_ITEMS;  // sorted items per union workgroup
+inline u64 ks_tiles(u64 m) { return (m + KS_TILE - 1) / KS_TILE; }
+struct KsSeg {  // one keyset; the table ends with a sentinel {nullptr, M}
+  const u64* keys;
+  u64 off;      // its first item among all keysets' items
+};
+// cat[p] = item p of the keysets laid end to end, set[p] = its keyset; *bad |= 1 when a keyset
+// is not strictly ascending (the neighbours are compared in the same pass).  segs: k + 1
+// entries (device).
+hipError_t launch_keysets_gather(const KsSeg* segs, int k, u64 m, u64* cat, uint8_t* set, u32* bad,
+                                 hipStream_t st);
+// The union of the m items in sorted order (item i is cat[idx[i]]; idx == nullptr: the
+// identity) and per union key the OR of 1 << set over its run: ukeys_d[0, m) always (device
+// scratch), ukeys / masks [0, cap) the first cap of them; *d_count = union keys.  Uses look-back
+// granules [0, ks_tiles(m)).
+hipError_t launch_keysets_union(const u64* cat, const uint8_t* set, const u32* idx, u64 m, u64* ukeys_d,
+                                u64* ukeys, u64* masks, u64 cap, const Scan& scan, u64* d_count,
+                                hipStream_t st);
+
 // ---- splice.hip (a sparse keyed join applied to a large state without merging it)
 // The keyed join of a small delta into a large state, as a splice: the state's rows of the
 // keyset K are taken out (launch_take_keys with the per-key index), joined with the delta
@@ -257,6 +280,11 @@ struct SortField {  // one column of the sort tuple
 };
 u64 sort_tiles(u64 n);
 size_t sort_tmp_bytes(u64 n);
+// The stable sort itself: *idx_out = the row numbers (u32, inside tmp) in the order of the nf
+// fields, least significant first (nullptr: the rows are in order already).  tmp:
+// sort_tmp_bytes(n); h_hist8 as below.
+hipError_t sort_fields(const SortField* fields, int nf, u64 n, void* tmp, u32** idx_out, u32* h_hist8,
+                       hipStream_t st);
 // rows sorted by (key, val, ts, node, cnt), exact duplicates dropped; *d_count = rows out.
 // h_hist8: 8 KB of pinned host memory (a digit pass whose byte is constant is skipped,
 // decided per field on the host: synchronizes once per field).

@@ -18,6 +18,7 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
                                                     -> ("ok", version', new_dots, changed, diffs)
     read(state, version, keys | "all")              -> ("ok", {key: value})
     take(state, version, keys)                      -> ("ok", value_map)
+    take_batch(state, version, [keys, ...])         -> ("ok", [value_map, ...])
     merkle_build(state, version, depth)             -> "ok"
     merkle_prepare(state, version, levels)          -> ("continue", bytes)
     merkle_continue(state, version, cont, levels, max_sync_size | "infinite")
@@ -72,6 +73,11 @@ class dgr_changed(C.Structure):
                 ("rows", dg_store), ("ctx", dg_context)]
 
 
+class dgr_taken(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("keys", C.c_void_p), ("masks", C.c_void_p), ("offs", C.c_void_p),
+                ("rows", dg_store)]
+
+
 VP, U64, I32 = C.c_void_p, C.c_uint64, C.c_int
 PU64 = C.POINTER(C.c_uint64)
 _SIGS = {
@@ -104,6 +110,10 @@ _SIGS = {
                              C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP), PU64]),
     "dgr_read": (I32, [VP, U64, I32, VP, U64, C.POINTER(VP), C.POINTER(VP), PU64]),
     "dgr_take": (I32, [VP, U64, VP, U64, C.POINTER(dg_store)]),
+    "dgr_take_batch": (I32, [VP, U64, I32, C.POINTER(VP), PU64, C.POINTER(dgr_taken)]),
+    # (its packing alone, host code: c_src/test_takes.c checks it)
+    "dgr_takes_words": (U64, [I32, PU64]),
+    "dgr_takes_pack": (U64, [VP, VP, I32, C.POINTER(VP), PU64, C.POINTER(VP), PU64]),
     "dgr_merkle_build": (I32, [VP, U64, C.c_uint32]),
     "dgr_merkle_prepare": (I32, [VP, U64, C.c_uint32, C.POINTER(VP), PU64]),
     "dgr_merkle_continue": (I32, [VP, U64, C.c_char_p, U64, C.c_uint32, U64, C.POINTER(I32),
@@ -549,6 +559,49 @@ def take(state: State, version: int, keys):
     return ("ok", _unmarshal_rows(eng, out))
 
 
+TAKE_BATCH_MAX = 64  # keysets per dgr_take_batch call (its masks are u64)
+
+
+def _take_batch_raw(state: State, version: int, kids):
+    """dgr_take_batch over marshalled keysets (at most TAKE_BATCH_MAX uint64 arrays): the
+    return code and the raw dgr_taken (host views, valid until the engine's next call)."""
+    eng = state.engine
+    k = len(kids)
+    kp = (VP * max(k, 1))(*[a.ctypes.data for a in kids])
+    kn = (C.c_uint64 * max(k, 1))(*[len(a) for a in kids])
+    tk = dgr_taken()
+    rc = eng.lib.dgr_take_batch(state.ptr, version, k, kp, kn, C.byref(tk))
+    return rc, tk
+
+
+def take_batch(state: State, version: int, keysets):
+    """take for k pending get_diff / send_diff messages as one call per 64 keysets
+    (dgr_take_batch): ("ok", [value_map_0, ...]), element j what take(state, version,
+    keysets[j])[1] is.  Every row of the union comes home and is unmarshalled ONCE; the
+    messages that hold a key share its value map."""
+    eng = state.engine
+    keysets = list(keysets)
+    out = []
+    for c0 in range(0, len(keysets), TAKE_BATCH_MAX):
+        kids = [_marshal_keys(eng, ks) for ks in keysets[c0:c0 + TAKE_BATCH_MAX]]
+        rc, tk = _take_batch_raw(state, version, kids)
+        if rc:
+            return _err(rc)
+        nu = int(tk.n_keys)
+        masks, offs = _arr(tk.masks, nu, np.uint64), _arr(tk.offs, nu + 1, np.uint64)
+        values = _unmarshal_rows(eng, tk.rows)  # {key term: entries}, every union row once
+        ukeys = _arr(tk.keys, nu, np.uint64)
+        held = [None] * nu  # per union key: (key term, its entries), None when the state lacks it
+        for i in range(nu):
+            if offs[i + 1] > offs[i]:
+                kt = eng.wrap(eng.universe.key_term(int(ukeys[i])))
+                held[i] = (kt, values[kt])
+        for j in range(len(kids)):
+            bit = 1 << j
+            out.append({h[0]: h[1] for i, h in enumerate(held) if h is not None and int(masks[i]) & bit})
+    return ("ok", out)
+
+
 def merkle_build(state: State, version: int, depth: int):
     eng = state.engine
     rc = eng.refresh_terms() or eng.lib.dgr_merkle_build(state.ptr, version, depth)
@@ -609,5 +662,6 @@ def resolve_keys(engine: Engine, keys):
 
 __all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "join_delta_diffs",
            "mutate_batch_diffs", "join_deltas", "join_deltas_diffs", "classify_diffs", "read", "take",
+           "take_batch",
            "merkle_build", "merkle_prepare", "merkle_continue", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

@@ -515,6 +515,57 @@ class Engine:
         out.n = int(so.n)
         return out
 
+    def take_keysets(self, s: Store, keysets, out: Store | None = None, cap_keys: int | None = None):
+        """Map.take(value, keys_j) for k <= 64 keysets out of one pass (dg_take_keysets): every
+        distinct key located once, every row copied once.  `keysets`: ascending unique device
+        int64 tensors.  Returns (ukeys, masks, offs, out): the union of the keysets, per union
+        key the bit mask of the keysets that hold it, offs[i]..offs[i + 1] its rows in `out`
+        (offs has len(ukeys) + 1 entries), and `out` the union's rows in store order.  Keyset
+        j's take is the concatenation of the ranges of the keys whose mask has bit j.
+        With `out` and `cap_keys` left to the call, a result that does not fit is taken again
+        at the sizes the call reports; given ones are used as they are, and a CapacityError
+        then carries the needed sizes as `.n_ukeys` and `.n_rows`."""
+        self._order()
+        k = len(keysets)
+        dummy = self._keys(torch.zeros(0, dtype=_I64, device=self.device))[0]
+        kp = (C.c_void_p * max(k, 1))(*[C.c_void_p(t.data_ptr()) if t.numel() else C.cast(dummy, C.c_void_p)
+                                       for t in keysets])
+        kn_np = np.array([int(t.numel()) for t in keysets] or [0], np.uint64)
+        kn = kn_np.ctypes.data_as(_abi.P64)
+        m = int(kn_np.sum())
+        own_out, own_cap = out is None, cap_keys is None
+        ss = s.abi()
+        for attempt in range(2):
+            if cap_keys is None:
+                cap_keys = m
+            if out is None:
+                out = Store.empty(min(max(s.n, 1), max(4 * m, 256)), self.device)
+            ukeys = torch.empty(max(cap_keys, 1), dtype=_I64, device=self.device)
+            masks = torch.empty(max(cap_keys, 1), dtype=_I64, device=self.device)
+            offs = torch.empty(cap_keys + 1, dtype=_I64, device=self.device)
+            so = out.abi()
+            nu = C.c_uint64(0)
+            rc = self.lib.dg_take_keysets(self.h, C.byref(ss), k, kp, kn, _ptr(ukeys, _abi.P64),
+                                          _ptr(masks, _abi.P64), _ptr(offs, _abi.P64), cap_keys, C.byref(nu),
+                                          C.byref(so))
+            if rc == _abi.DG_E_CAPACITY:
+                if attempt == 0 and (own_out or int(so.n) <= out.cap) and (own_cap or nu.value <= cap_keys):
+                    if int(so.n) > out.cap:
+                        out = Store.empty(int(so.n), self.device)
+                    if nu.value > cap_keys:
+                        cap_keys = int(nu.value)
+                    continue
+                try:
+                    check(rc)
+                except _abi.CapacityError as err:
+                    err.n_ukeys, err.n_rows = int(nu.value), int(so.n)
+                    raise
+            check(rc)
+            break
+        out.n = int(so.n)
+        n = int(nu.value)
+        return ukeys[:n], masks[:n], offs[:n + 1], out
+
     def mutate_batch(self, state: Store, ctx: Context, node: int, kind: torch.Tensor,
                      key: torch.Tensor, val: torch.Tensor, ts: torch.Tensor,
                      add_rank: torch.Tensor, n_adds: int):

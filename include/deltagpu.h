@@ -457,6 +457,32 @@ int dg_join_deltas(dg_engine* e, dg_store* state, dg_context* state_ctx, int k, 
 int dg_take_keys(dg_engine* e, const dg_store* s, const uint64_t* keys, uint64_t n_keys,
                  dg_store* out);
 
+/* The values of k pending sync deltas out of one pass: the k keysets of k {:get_diff, diff,
+ * keys} / send_diff messages (keys[j][0, n_keys[j]): device arrays, each ascending and unique,
+ * as dg_join_deltas takes them; 0 <= k <= 64, DG_E_INVAL beyond; n_keys[j] == 0 allowed).
+ * A replica's neighbours mostly ask for the same keys, so every distinct key is located once
+ * and every row copied once:
+ *   ukeys[0, *n_ukeys)   the union of the keysets, ascending and unique.  A key the store does
+ *                        not hold stays in it (the receiver's join over `keys` is what removes
+ *                        a key, so an absent key is part of the message).
+ *   masks[i]             bit j set iff keyset j holds ukeys[i] (never zero).
+ *   offs[0, *n_ukeys]    out's rows [offs[i], offs[i + 1]) are the rows of ukeys[i], in store
+ *                        order (an absent key: an empty range); offs[*n_ukeys] == out->n.
+ *   out                  the rows of `s` whose key is in the union, each once, in store order:
+ *                        what dg_take_keys(s, ukeys, *n_ukeys) gives.
+ * Message j's Map.take(value, keys_j) is the concatenation of the ranges of the keys whose
+ * mask has bit j, bit-identical to dg_take_keys(s, keys[j], n_keys[j]).
+ * ukeys and masks hold cap_keys entries and offs cap_keys + 1; cap_keys = Σ n_keys[j] always
+ * suffices.  More union keys than cap_keys or more rows than out->cap: DG_E_CAPACITY with the
+ * needed sizes in *n_ukeys and out->n (the arrays then hold a prefix, or nothing).  A keyset
+ * that is not strictly ascending: DG_E_ORDER (verified on the device in the pass that reads
+ * the keysets; a wrong union would ship wrong deltas silently).  k == 0 or only empty
+ * keysets: *n_ukeys = 0, out->n = 0, offs[0] = 0.  ukeys, masks, offs and out's columns may
+ * be memory from dg_host_alloc.  Only reads `s`.  Synchronous. */
+int dg_take_keysets(dg_engine* e, const dg_store* s, int k, const uint64_t* const* keys,
+                    const uint64_t* n_keys, uint64_t* ukeys, uint64_t* masks, uint64_t* offs,
+                    uint64_t cap_keys, uint64_t* n_ukeys, dg_store* out);
+
 /* ---- batched mutations ----------------------------------------------------- */
 /* A batch of AWLWWMap.add/4 and remove/3 operations by node `node` as ONE delta
  * (aw_lww_map.ex:99-146; CausalCrdt applies each op's delta with keys = [key] as the op
