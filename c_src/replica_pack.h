@@ -1,0 +1,60 @@
+/*
+ * replica_pack.h — the replica layer's host layouts, each stated once: rows and a context as
+ * columns at one stride, the packed messages, the return block, a continuation's byte frame.
+ * Host code only (replica_pack.c calls no dg_* function); internal, not the NIF's surface.
+ */
+#ifndef DG_REPLICA_PACK_H
+#define DG_REPLICA_PACK_H
+
+#include "../include/deltagpu.h"
+
+static inline uint64_t even(uint64_t w) { return (w + 1) & ~UINT64_C(1); } /* 16-B aligned offsets */
+static inline uint64_t rows_words(uint64_t n) { return 4 * even(n) + even((n + 1) / 2); }
+static inline uint64_t ctx_words(uint64_t n) { return even(n) + even((n + 1) / 2); }
+
+/* Rows as five columns `stride` words apart: key | val | ts | cnt | node (u32) from `base`
+ * (the column order; dg_store's fields name node before cnt). */
+dg_store rp_rows(uint64_t* base, uint64_t stride, uint64_t n, uint64_t cap);
+/* A context as two columns `stride` words apart: cnt | node (u32). */
+dg_context rp_ctx(uint64_t* base, uint64_t stride, int32_t kind, uint64_t n, uint64_t cap);
+
+/* host rows / a host context into the message `hb` at word o, columns at stride even(n);
+ * *dev = the view of the same place in its device copy `db`.  Returns the next free word. */
+uint64_t rp_pack_rows(uint64_t* hb, uint64_t* db, uint64_t o, const dg_store* r, dg_store* dev);
+uint64_t rp_pack_ctx(uint64_t* hb, uint64_t* db, uint64_t o, const dg_context* c, dg_context* dev);
+/* keys -> ascending unique at dst; returns their number */
+uint64_t rp_sort_unique(const uint64_t* keys, uint64_t n, uint64_t* dst);
+/* host rows in store order without duplicates / a context in its kind's order (O(n) walks) */
+int rp_rows_sorted(const dg_store* s);
+int rp_ctx_sorted(const dg_context* c);
+
+/* The return block for S changed keys / rows and a context of C entries (words): changed
+ * keys [0, S) | key | val | ts | cnt [S, 5S) | node u32 [5S, 6S) | context cnt [6S, 6S + C) |
+ * context node u32 [6S + C, 6S + 2C) | the changed keys' old value ids [D, D + S) | new
+ * [D + S, D + 2S) | flags u8 [D + 2S, D + 2S + S / 8], D = 6S + 2C (the *_diffs calls).  The
+ * kernels write it and the term layers read these views of it (here empty: n = 0, a VV). */
+static inline uint64_t rp_back_words(uint64_t S, uint64_t C) { return 6 * S + 2 * C + 2 * S + S / 8 + 1; }
+static inline uint64_t* rp_back_keys(uint64_t* b) { return b; }
+static inline dg_store rp_back_rows(uint64_t* b, uint64_t S) { return rp_rows(b + S, S, 0, S); }
+static inline dg_context rp_back_ctx(uint64_t* b, uint64_t S, uint64_t C) {
+  return rp_ctx(b + 6 * S, C, DG_CTX_VV, 0, C);
+}
+static inline dg_lww_diffs rp_back_diffs(uint64_t* b, uint64_t S, uint64_t C) {
+  uint64_t* d = b + 6 * S + 2 * C;
+  return (dg_lww_diffs){d, d + S, (uint8_t*)(d + 2 * S), S};
+}
+/* the least S with n bytes at the block's head, the 6 S words before the context (dgr_sweep) */
+static inline uint64_t rp_back_s_for_bytes(uint64_t n) { return (n + 6 * 8 - 1) / (6 * 8); }
+
+/* A continuation as bytes (replica.h dgr_merkle_prepare): a 20-byte header, then the words
+ * pos[n] | hash[n] | bucket[n_buckets]. */
+#define RP_CONT_HEAD 20
+static inline uint64_t rp_cont_bytes(uint64_t n, uint64_t nb) { return RP_CONT_HEAD + 8 * (2 * n + nb); }
+/* writes the header; returns where pos | hash | bucket go */
+uint8_t* rp_cont_write_head(uint8_t* bin, uint32_t level, uint64_t n, uint64_t n_buckets);
+/* the header of a frame of `len` bytes read and checked against len (DG_E_INVAL) */
+int rp_cont_parse(const uint8_t* bin, uint64_t len, uint32_t* level, uint64_t* n, uint64_t* n_buckets);
+/* the continuation whose pos | hash | bucket run stands at `base` (full: n = cap) */
+dg_merkle_cont rp_cont_at(uint64_t* base, uint32_t level, uint64_t n, uint64_t n_buckets);
+
+#endif /* DG_REPLICA_PACK_H */

@@ -366,7 +366,7 @@ def test_join_delta_retries_an_aborted_grid(monkeypatch):
 # ---------------------------------------------------------------- dg_join_delta_home
 # The fused small-delta path (csrc/small.hip): one launch chain, one host wait, the
 # result in page-locked memory -- what the NIF's join_delta / mutate_batch use for
-# mutations and small sync deltas (c_src/replica.c).
+# mutations and small sync deltas (c_src/replica_join.c).
 
 @pytest.mark.parametrize("n_keys", [30_000, 300_000])
 def test_mutation_sequence_home(engine, n_keys):

@@ -1,5 +1,5 @@
 """A batch of sync deltas through the device-resident replica, through the NIF's mirror
-(delta_crdt_ex_amd/nif.py join_deltas_diffs -> c_src/replica.c dgr_join_deltas_diffs ->
+(delta_crdt_ex_amd/nif.py join_deltas_diffs -> c_src/replica_join.c dgr_join_deltas_diffs ->
 dg_join_deltas): twin states, one taking the batch in one call and one taking the same
 deltas one by one, end in the same rows, context and tree; the batch's diffs are the NET
 diffs (the term oracle's read before the first and after the last delta, classified as

@@ -1,5 +1,5 @@
 """on_diffs served by the device-resident replica, through the NIF's mirror
-(delta_crdt_ex_amd/nif.py -> c_src/replica.c dgr_join_delta_diffs / dgr_mutate_batch_diffs ->
+(delta_crdt_ex_amd/nif.py -> c_src/replica_join.c dgr_join_delta_diffs / dgr_mutate_batch_diffs ->
 dg_join_delta_home_diffs or dg_join_delta_diffs): the diffs list every call returns equals
 diffs_to_callback/3's rule (causal_crdt.ex:361-381) applied to the term oracle's reads
 before and after -- and a replica that uses ONLY those lists, reading no old struct,

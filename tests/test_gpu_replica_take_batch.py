@@ -1,5 +1,5 @@
 """k pending get_diff / send_diff messages answered by ONE call on the device-resident
-replica, through the NIF's mirror (delta_crdt_ex_amd/nif.py take_batch -> c_src/replica.c
+replica, through the NIF's mirror (delta_crdt_ex_amd/nif.py take_batch -> c_src/replica_take.c
 dgr_take_batch -> dg_take_keysets): element j equals take(state, version, keysets[j]) and
 the term oracle's Map.take, for keysets given unsorted, with duplicates and with keys the state
 lacks; more than 64 keysets are chunked; the version does not move; an older version is

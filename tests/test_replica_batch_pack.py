@@ -1,4 +1,4 @@
-"""The packed message of a batch of deltas (c_src/replica.c dgr_batch_words / dgr_batch_pack)
+"""The packed message of a batch of deltas (c_src/replica_pack.c dgr_batch_words / dgr_batch_pack)
 on the host: c_src/test_batch.c, a plain executable, checks the offsets of every delta's rows,
 context and keyset, their 16-byte alignment, that they neither overlap nor leave the message,
 their contents, and the keysets' sort-unique.  No device is opened."""

@@ -1,4 +1,4 @@
-"""The packed message of a batch of keysets (c_src/replica.c dgr_takes_words / dgr_takes_pack)
+"""The packed message of a batch of keysets (c_src/replica_pack.c dgr_takes_words / dgr_takes_pack)
 on the host: c_src/test_takes.c, a plain executable, checks that every keyset lies sorted and
 unique at its documented 16-byte aligned offset (given unsorted with duplicates, ascending
 already, or ascending but for one pair), that the device views name the same places,
