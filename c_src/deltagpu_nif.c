@@ -47,6 +47,8 @@
  *   merkle_build(state, version, depth)                -> :ok
  *   merkle_prepare(state, version, levels)             -> {:continue, cont}     (:255)
  *   merkle_continue(state, version, cont, levels, max) -> {:continue, cont} | {:ok, keys}
+ *   merkle_continue_batch(state, version, [cont, ...], levels, max)
+ *                                                      -> {:ok, [{:continue, cont} | {:ok, keys}, ...]}
  *        (:96-105; `max` is max_sync_size or :infinite, :98,105,206-214; a key this node
  *        never interned comes back as {:"$dg_key", id})
  *   resolve_keys(engine, keys)                         -> keys (placeholders -> terms)
@@ -1178,6 +1180,64 @@ out:
   return r;
 }
 
+/* merkle_continue_batch(state, version, [cont, ...], levels, max_sync_size | :infinite)
+ *   -> {:ok, [{:continue, cont} | {:ok, keys}, ...]}: merkle_continue/5 for k pending
+ * {:diff, %Diff{continuation: ...}} messages, one dgr_merkle_continue_batch (one launch and one
+ * wait for the messages within the one-workgroup limits) per 64.  Element j is what
+ * merkle_continue/5 returns for message j, an {:error, _} included; all are answered against
+ * the state as it is at the call, and a stale version fails the whole call. */
+static ERL_NIF_TERM merkle_continue_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  state_res* s;
+  uint64_t version;
+  unsigned total, levels;
+  ErlNifUInt64 max_sync = UINT64_MAX;
+  if (!get_state(env, argv[0], argv[1], &s, &version) || !enif_get_list_length(env, argv[2], &total) ||
+      !enif_get_uint(env, argv[3], &levels) ||
+      (!enif_is_identical(argv[4], A_INFINITE) && !enif_get_uint64(env, argv[4], &max_sync)))
+    return enif_make_badarg(env);
+  engine_res* g = s->eng;
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  const uint8_t* bins[DG_CONT_BATCH_MAX];
+  uint64_t lens[DG_CONT_BATCH_MAX];
+  dgr_cont_result res[DG_CONT_BATCH_MAX];
+  ERL_NIF_TERM* out = (ERL_NIF_TERM*)enif_alloc((total ? total : 1) * sizeof *out);
+  ERL_NIF_TERM r, h, t = argv[2];
+  unsigned done = 0;
+  if (!out) TRY(DG_E_NOMEM);
+  TRY(refresh_terms(g));
+  while (done < total) {
+    int k = 0;
+    while (k < DG_CONT_BATCH_MAX && enif_get_list_cell(env, t, &h, &t)) {
+      ErlNifBinary in;
+      if (!enif_inspect_binary(env, h, &in)) TRY(DG_E_INVAL);
+      bins[k] = in.data;
+      lens[k] = in.size;
+      k++;
+    }
+    if (k == 0) TRY(DG_E_INVAL);
+    TRY(dgr_merkle_continue_batch(s->s, version, k, bins, lens, levels, max_sync, res));
+    for (int j = 0; j < k; j++) {
+      if (res[j].rc) {
+        out[done + j] = error_term(env, res[j].rc);
+      } else if (res[j].status == 1) {
+        out[done + j] = enif_make_tuple2(env, A_CONTINUE, bytes_term(env, res[j].bin, res[j].len));
+      } else {
+        ERL_NIF_TERM l = enif_make_list(env, 0);
+        for (uint64_t i = res[j].n_keys; i-- > 0;) l = enif_make_list_cell(env, key_term(env, g, res[j].keys[i]), l);
+        out[done + j] = enif_make_tuple2(env, A_OK, l);
+      }
+    }
+    done += (unsigned)k;
+  }
+out:
+  r = rc ? error_term(env, rc) : enif_make_tuple2(env, A_OK, enif_make_list_from_array(env, out, total));
+  if (out) enif_free(out);
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
 /* resolve_keys(engine, keys) -> keys: placeholders of keys this node knows -> their terms
  * (the others stay placeholders) */
 static ERL_NIF_TERM resolve_keys_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
@@ -1237,6 +1297,7 @@ static ErlNifFunc funcs[] = {
     {"merkle_build", 3, merkle_build_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_prepare", 3, merkle_prepare_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_continue", 5, merkle_continue_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"merkle_continue_batch", 5, merkle_continue_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"resolve_keys", 2, resolve_keys_nif, 0},
     {"sweep", 1, sweep_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };

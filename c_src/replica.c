@@ -117,6 +117,7 @@ int dgr_engine_close(dgr_engine* g) {
   dg_buffer_free(e, g->d_ckeys);
   dg_host_free(e, g->h_ckeys);
   dg_host_free(e, g->h_cstage);
+  dg_host_free(e, g->h_bstage);
   free(g->h_bin);
   free(g->sw_stores);
   free(g->b_rows); /* (and b_ctx, b_keys, b_nk, b_unsorted behind it) */

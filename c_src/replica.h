@@ -225,6 +225,30 @@ int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint
                         uint32_t levels, uint64_t max_sync, int* status, const uint8_t** out_bin,
                         uint64_t* out_len, const uint64_t** keys, uint64_t* n_keys);
 
+/* dgr_merkle_continue for k pending {:diff, %Diff{continuation: ...}} messages (k neighbours'
+ * hops) as one call: element j of `results` is what dgr_merkle_continue returns for message j
+ * -- rc its return code, and under rc == DG_OK status, the next continuation's bytes or the
+ * keys, byte for byte.  The messages within dg_merkle_continue_home's limits are unpacked into
+ * the one page-locked message buffer and answered by ONE dg_merkle_continues launch and wait,
+ * their outputs carved from one page-locked block (replica_pack.h rp_cont_carve); a hop that
+ * reports DG_E_CAPACITY is retried once, with the other such hops.  A message over the limits,
+ * one of a level above depth + 1, one with more keys than were kept, and every message under
+ * DGR_CONT_GENERAL, goes through dgr_merkle_continue's general calls, one by one, afterwards.
+ * ALL k answers are computed against the state as it is at the call.  The frames lie end to
+ * end in the engine's byte buffer; they and the keys are host views, valid until the next call
+ * on the engine.  The version is checked once: DGR_E_STALE fails the whole call.  DG_E_INVAL
+ * for k < 0, k > DG_CONT_BATCH_MAX (the term layers chunk by 64), a null argument or no tree. */
+typedef struct dgr_cont_result {
+  int rc;
+  int status;
+  const uint8_t* bin;
+  uint64_t len;
+  const uint64_t* keys;
+  uint64_t n_keys;
+} dgr_cont_result;
+int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
+                              const uint64_t* lens, uint32_t levels, uint64_t max_sync, dgr_cont_result* results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,9 @@ struct dgr_engine {
   uint64_t ckeys_cap, h_ckeys_cap, h_cstage_cap;
   uint8_t* h_bin;
   uint64_t bin_cap;
+  /* dgr_merkle_continue_batch: the k hops' outputs (page-locked, replica_pack.h rp_cont_carve) */
+  uint64_t* h_bstage;
+  uint64_t h_bstage_cap;
   /* dgr_sweep: the live states' stores as one host array */
   dg_store* sw_stores;
   uint64_t sw_cap;

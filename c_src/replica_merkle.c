@@ -35,29 +35,36 @@ int dgr_merkle_build(dgr_state* s, uint64_t version, uint32_t depth) {
   return DG_OK;
 }
 
-#define CONT_SMALL_OUT 65536 /* entries of an outgoing continuation / keys kept in host memory */
+#define CONT_SMALL_OUT RP_CONT_SMALL_OUT
 
-/* a continuation in host memory (the kernel wrote it there, or it was staged there) framed as
- * the message */
-static int frame_cont(dgr_engine* g, const dg_merkle_cont* co, const uint8_t** bin, uint64_t* len) {
-  const uint64_t bytes = rp_cont_bytes(co->n, co->n_buckets);
-  if (g->bin_cap < bytes) {
-    uint8_t* p = (uint8_t*)realloc(g->h_bin, bytes);
+/* `bytes` bytes of the engine's byte buffer from offset `at` on (what stands before is kept) */
+static int bin_room(dgr_engine* g, uint64_t at, uint64_t bytes) {
+  if (g->bin_cap < at + bytes) {
+    const uint64_t cap = at ? umax(at + bytes, 2 * g->bin_cap) : bytes;
+    uint8_t* p = (uint8_t*)realloc(g->h_bin, cap);
     if (!p) return DG_E_NOMEM;
     g->h_bin = p;
-    g->bin_cap = bytes;
+    g->bin_cap = cap;
   }
-  uint8_t* data = rp_cont_write_head(g->h_bin, co->level, co->n, co->n_buckets);
+  return DG_OK;
+}
+
+/* a continuation in host memory (the kernel wrote it there, or it was staged there) framed as
+ * the message, `at` bytes into the engine's byte buffer (a batch lays its frames end to end) */
+static int frame_cont(dgr_engine* g, uint64_t at, const dg_merkle_cont* co, const uint8_t** bin, uint64_t* len) {
+  const uint64_t bytes = rp_cont_bytes(co->n, co->n_buckets);
+  TRY(bin_room(g, at, bytes));
+  uint8_t* data = rp_cont_write_head(g->h_bin + at, co->level, co->n, co->n_buckets);
   memcpy(data, co->pos, 8 * co->n);
   memcpy(data + 8 * co->n, co->hash, 8 * co->n);
   if (co->n_buckets) memcpy(data + 16 * co->n, co->bucket, 8 * co->n_buckets);
-  *bin = g->h_bin;
+  *bin = g->h_bin + at;
   *len = bytes;
   return DG_OK;
 }
 
 /* a device continuation -> bytes */
-static int cont_to_bytes(dgr_engine* g, const dg_merkle_cont* c, const uint8_t** bin, uint64_t* len) {
+static int cont_to_bytes(dgr_engine* g, uint64_t at, const dg_merkle_cont* c, const uint8_t** bin, uint64_t* len) {
   /* staged 8-byte aligned in page-locked memory (one wait), then framed */
   TRY(ri_grow(g, &g->h_cstage, NULL, &g->h_cstage_cap, umax(2 * c->n + c->n_buckets, 1)));
   const dg_merkle_cont st = rp_cont_at(g->h_cstage, c->level, c->n, c->n_buckets);
@@ -65,7 +72,7 @@ static int cont_to_bytes(dgr_engine* g, const dg_merkle_cont* c, const uint8_t**
   TRY(dg_copy_async(g->e, st.hash, c->hash, c->n * 8));
   TRY(dg_copy_async(g->e, st.bucket, c->bucket, c->n_buckets * 8));
   TRY(dg_engine_sync(g->e));
-  return frame_cont(g, &st, bin, len);
+  return frame_cont(g, at, &st, bin, len);
 }
 
 int dgr_merkle_prepare(dgr_state* s, uint64_t version, uint32_t levels, const uint8_t** bin, uint64_t* len) {
@@ -82,37 +89,35 @@ int dgr_merkle_prepare(dgr_state* s, uint64_t version, uint32_t levels, const ui
     co.hash = g->h_cstage + n;
     co.cap = n;
     TRY(dg_merkle_prepare(g->e, &s->tree, levels, &co));
-    return frame_cont(g, &co, bin, len);
+    return frame_cont(g, 0, &co, bin, len);
   }
   TRY(grow_cont(g, &g->co, n, 1));
   g->co.n = g->co.n_buckets = 0;
   TRY(dg_merkle_prepare(g->e, &s->tree, levels, &g->co));
-  return cont_to_bytes(g, &g->co, bin, len);
+  return cont_to_bytes(g, 0, &g->co, bin, len);
 }
 
 /* One hop through dg_merkle_continue_home: the incoming continuation read where it was
  * unpacked (mapped memory), the next one (truncated to max_sync) or the keys written by
  * the kernel into page-locked memory, one launch and one wait.  *done = 0: over its
  * limits (nothing happened; the general path runs). */
-static int continue_small(dgr_state* s, uint32_t level, uint64_t n, uint64_t nb, uint32_t levels,
+static int cont_general(void) { /* DGR_CONT_GENERAL=1: always the general calls (A/B) */
+  static int general = -1;
+  if (general < 0) general = getenv("DGR_CONT_GENERAL") != NULL;
+  return general;
+}
+
+static int continue_small(dgr_state* s, uint64_t at, uint32_t level, uint64_t n, uint64_t nb, uint32_t levels,
                           uint64_t max_sync, int* status, const uint8_t** out_bin, uint64_t* out_len,
                           const uint64_t** keys, uint64_t* n_keys, int* done) {
   dgr_engine* g = s->g;
   *done = 0;
-  static int general = -1; /* DGR_CONT_GENERAL=1: always the general calls (A/B) */
-  if (general < 0) general = getenv("DGR_CONT_GENERAL") != NULL;
   const uint32_t depth = s->tree.depth;
-  if (general || n > DG_CONT_HOME_ENTRIES || nb > DG_CONT_HOME_BUCKETS || level > depth + 1) return DG_OK;
+  if (cont_general() || n > DG_CONT_HOME_ENTRIES || nb > DG_CONT_HOME_BUCKETS || level > depth + 1) return DG_OK;
   const dg_merkle_cont ci = rp_cont_at(g->h_msg, level, n, nb);
-  uint64_t C, CB = umax(umin(n, max_sync), 1);
-  if (level < depth) {
-    const uint32_t k = levels < depth - level ? levels : depth - level;
-    C = umin(n << k, max_sync);
-  } else {
-    C = umax(4 * umin(n, max_sync), 64);
-  }
-  C = umax(C, 1);
-  const uint64_t kcap = umax(umin(umin(max_sync, s->rows.n + n + 1), CONT_SMALL_OUT), 1);
+  const rp_cont_room room = rp_cont_room_for(level, n, depth, levels, max_sync, s->rows.n);
+  uint64_t C = room.C, CB = room.CB;
+  const uint64_t kcap = room.kcap;
   TRY(ri_grow(g, &g->h_ckeys, NULL, &g->h_ckeys_cap, kcap));
   uint64_t nk = 0, ntot = 0;
   dg_merkle_cont co;
@@ -143,17 +148,16 @@ static int continue_small(dgr_state* s, uint32_t level, uint64_t n, uint64_t nb,
     *done = 1;
     return DG_OK;
   }
-  TRY(frame_cont(g, &co, out_bin, out_len));
+  TRY(frame_cont(g, at, &co, out_bin, out_len));
   *done = 1;
   return DG_OK;
 }
 
-int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint64_t len, uint32_t levels,
-                        uint64_t max_sync, int* status, const uint8_t** out_bin, uint64_t* out_len,
-                        const uint64_t** keys, uint64_t* n_keys) {
-  if (!s || !bin || !status || !out_bin || !out_len || !keys || !n_keys || !s->has_tree || len < RP_CONT_HEAD)
-    return DG_E_INVAL;
-  TRY(check_version(s, version));
+/* dgr_merkle_continue behind its version check, the next continuation framed `at` bytes into
+ * the engine's byte buffer */
+static int continue_at(dgr_state* s, uint64_t at, const uint8_t* bin, uint64_t len, uint32_t levels,
+                       uint64_t max_sync, int* status, const uint8_t** out_bin, uint64_t* out_len,
+                       const uint64_t** keys, uint64_t* n_keys) {
   dgr_engine* g = s->g;
   uint32_t level;
   uint64_t n, nb;
@@ -166,7 +170,7 @@ int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint
   TRY(ri_grow_msg(g, 2 * n + nb + 1));
   if (2 * n + nb) memcpy(g->h_msg, bin + RP_CONT_HEAD, (2 * n + nb) * 8);
   int done = 0;
-  TRY(continue_small(s, level, n, nb, levels, max_sync, status, out_bin, out_len, keys, n_keys, &done));
+  TRY(continue_small(s, at, level, n, nb, levels, max_sync, status, out_bin, out_len, keys, n_keys, &done));
   if (done) return DG_OK;
   *status = 0;
   TRY(dg_copy_async(g->e, g->d_msg, g->h_msg, (2 * n + nb) * 8));
@@ -188,7 +192,7 @@ int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint
   TRY(rc);
   if (*status == 1) {
     if (max_sync != UINT64_MAX) TRY(dg_merkle_truncate(g->e, &s->tree, &g->co, max_sync)); /* :98 */
-    return cont_to_bytes(g, &g->co, out_bin, out_len);
+    return cont_to_bytes(g, at, &g->co, out_bin, out_len);
   }
   /* {:ok, keys}: the first max_sync_size differing keys (Enum.take, :105) */
   TRY(ri_grow(g, &g->h_ckeys, NULL, &g->h_ckeys_cap, umax(nk, 1)));
@@ -196,5 +200,163 @@ int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint
   TRY(dg_engine_sync(g->e));
   *keys = g->h_ckeys;
   *n_keys = nk;
+  return DG_OK;
+}
+
+int dgr_merkle_continue(dgr_state* s, uint64_t version, const uint8_t* bin, uint64_t len, uint32_t levels,
+                        uint64_t max_sync, int* status, const uint8_t** out_bin, uint64_t* out_len,
+                        const uint64_t** keys, uint64_t* n_keys) {
+  if (!s || !bin || !status || !out_bin || !out_len || !keys || !n_keys || !s->has_tree || len < RP_CONT_HEAD)
+    return DG_E_INVAL;
+  TRY(check_version(s, version));
+  return continue_at(s, 0, bin, len, levels, max_sync, status, out_bin, out_len, keys, n_keys);
+}
+
+/* One dg_merkle_continues call over the hops `idx[0, m)`: hop idx[i]'s input where it was
+ * unpacked (h_msg + moff), its outputs in room[i] at off[i] of `block`. */
+typedef struct batch_hop {
+  uint32_t level;
+  uint64_t n, nb, moff; /* the continuation; its words in h_msg */
+  int general;          /* answered by the general calls */
+  int64_t bin_at, keys_at; /* byte offsets in h_bin (-1: none) */
+} batch_hop;
+
+static int continue_hops(dgr_state* s, const batch_hop* bh, const int* idx, int m, uint64_t* block,
+                         const rp_cont_room* room, const uint64_t* off, uint32_t levels, uint64_t max_sync,
+                         dg_merkle_cont* cin, dg_merkle_cont* cout, dg_cont_hop* hops) {
+  dgr_engine* g = s->g;
+  for (int i = 0; i < m; i++) {
+    const batch_hop* b = &bh[idx[i]];
+    cin[i] = rp_cont_at(g->h_msg + b->moff, b->level, b->n, b->nb);
+    cout[i] = rp_cont_room_out(block, off[i], room[i]);
+    memset(&hops[i], 0, sizeof hops[i]);
+    hops[i].in = &cin[i];
+    hops[i].out = &cout[i];
+    hops[i].keys = room[i].kcap ? rp_cont_room_keys(block, off[i], room[i]) : NULL;
+    hops[i].cap = room[i].kcap;
+  }
+  return dg_merkle_continues(g->e, &s->tree, &s->rows, m, hops, levels, max_sync);
+}
+
+int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
+                              const uint64_t* lens, uint32_t levels, uint64_t max_sync, dgr_cont_result* results) {
+  if (!s || k < 0 || k > DG_CONT_BATCH_MAX || (k && (!bins || !lens || !results)) || levels < 1) return DG_E_INVAL;
+  for (int j = 0; j < k; j++)
+    if (!bins[j]) return DG_E_INVAL;
+  if (!s->has_tree) return DG_E_INVAL;
+  TRY(check_version(s, version));
+  if (k == 0) return DG_OK;
+  dgr_engine* g = s->g;
+  const uint32_t depth = s->tree.depth;
+  batch_hop bh[DG_CONT_BATCH_MAX];
+  int idx[DG_CONT_BATCH_MAX], m = 0; /* the hops of the launch */
+  rp_cont_room room[DG_CONT_BATCH_MAX];
+  uint64_t off[DG_CONT_BATCH_MAX + 1], words = 0;
+  memset(results, 0, (size_t)k * sizeof *results);
+  for (int j = 0; j < k; j++) {
+    batch_hop* b = &bh[j];
+    memset(b, 0, sizeof *b);
+    b->bin_at = b->keys_at = -1;
+    results[j].rc = lens[j] < RP_CONT_HEAD ? DG_E_INVAL : rp_cont_parse(bins[j], lens[j], &b->level, &b->n, &b->nb);
+    if (results[j].rc != DG_OK) continue;
+    const rp_cont_room r = rp_cont_room_for(b->level, b->n, depth, levels, max_sync, s->rows.n);
+    b->general = cont_general() || b->n > DG_CONT_HOME_ENTRIES || b->nb > DG_CONT_HOME_BUCKETS ||
+                 b->level > depth + 1 || r.C > CONT_SMALL_OUT;
+    if (b->general) continue;
+    b->moff = words;
+    words += even(2 * b->n + b->nb);
+    room[m] = r;
+    idx[m++] = j;
+  }
+  if (m == 1) { /* one hop for the launch: the single call's own launch is 5-6 us shorter (bench_hops) */
+    bh[idx[0]].general = 1;
+    m = 0;
+  }
+  dg_merkle_cont cin[DG_CONT_BATCH_MAX], cout[DG_CONT_BATCH_MAX];
+  dg_cont_hop hops[DG_CONT_BATCH_MAX];
+  uint64_t at = 0; /* bytes of h_bin in use */
+  if (m) {
+    /* the m continuations as one message: pos | hash | bucket each, where the kernel reads them */
+    TRY(ri_grow_msg(g, words + 1));
+    for (int i = 0; i < m; i++) {
+      const batch_hop* b = &bh[idx[i]];
+      if (2 * b->n + b->nb) memcpy(g->h_msg + b->moff, bins[idx[i]] + RP_CONT_HEAD, (2 * b->n + b->nb) * 8);
+    }
+    TRY(ri_grow(g, &g->h_bstage, NULL, &g->h_bstage_cap, umax(rp_cont_carve(m, room, off), 1)));
+    TRY(continue_hops(s, bh, idx, m, g->h_bstage, room, off, levels, max_sync, cin, cout, hops));
+    /* DG_E_CAPACITY: one retry at the sizes reported, with only the hops that reported it (their
+     * outputs staged where a single hop's are: a node form's answer has no keys) */
+    int ridx[DG_CONT_BATCH_MAX], rpos[DG_CONT_BATCH_MAX], rm = 0;
+    rp_cont_room rroom[DG_CONT_BATCH_MAX];
+    for (int i = 0; i < m; i++) {
+      if (hops[i].rc != DG_E_CAPACITY) continue;
+      const rp_cont_room r = {umax(cout[i].n, room[i].C), umax(cout[i].n_buckets, room[i].CB), 0};
+      if (r.C > CONT_SMALL_OUT) {
+        bh[idx[i]].general = 1;
+        continue;
+      }
+      rroom[rm] = r;
+      rpos[rm] = i;
+      ridx[rm++] = idx[i];
+    }
+    if (rm) {
+      dg_merkle_cont rin[DG_CONT_BATCH_MAX], rout[DG_CONT_BATCH_MAX];
+      dg_cont_hop rhops[DG_CONT_BATCH_MAX];
+      uint64_t roff[DG_CONT_BATCH_MAX + 1];
+      TRY(ri_grow(g, &g->h_cstage, NULL, &g->h_cstage_cap, umax(rp_cont_carve(rm, rroom, roff), 1)));
+      TRY(continue_hops(s, bh, ridx, rm, g->h_cstage, rroom, roff, levels, max_sync, rin, rout, rhops));
+      for (int i = 0; i < rm; i++) {
+        hops[rpos[i]] = rhops[i];
+        cout[rpos[i]] = rout[i];
+      }
+    }
+    for (int i = 0; i < m; i++) {
+      const int j = idx[i];
+      if (bh[j].general) continue;
+      dgr_cont_result* r = &results[j];
+      r->rc = hops[i].rc;
+      if (r->rc != DG_OK) continue;
+      if (hops[i].status == DG_CONT_DECLINED) {
+        bh[j].general = 1;
+      } else if (hops[i].status == 0) {
+        if (hops[i].n_total > hops[i].n_keys && hops[i].n_keys < max_sync) {
+          bh[j].general = 1; /* more keys than kept here */
+          continue;
+        }
+        r->keys = hops[i].keys;
+        r->n_keys = hops[i].n_keys;
+      } else {
+        const uint8_t* p;
+        r->status = 1;
+        r->rc = frame_cont(g, at, &cout[i], &p, &r->len);
+        if (r->rc != DG_OK) return r->rc;
+        bh[j].bin_at = (int64_t)at;
+        at += (r->len + 7) & ~UINT64_C(7);
+      }
+    }
+  }
+  /* the rest through the general calls, one by one (they reuse the message buffer and the
+   * single hop's staging; what the launch answered is framed by now) */
+  for (int j = 0; j < k; j++) {
+    if (!bh[j].general) continue;
+    dgr_cont_result* r = &results[j];
+    const uint8_t* p = NULL;
+    const uint64_t* keys = NULL;
+    r->rc = continue_at(s, at, bins[j], lens[j], levels, max_sync, &r->status, &p, &r->len, &keys, &r->n_keys);
+    if (r->rc != DG_OK) continue;
+    if (r->status == 1) {
+      bh[j].bin_at = (int64_t)at;
+      at += (r->len + 7) & ~UINT64_C(7);
+    } else if (r->n_keys) { /* the keys out of the single hop's buffer, which the next hop reuses */
+      TRY(bin_room(g, at, r->n_keys * 8));
+      memcpy(g->h_bin + at, keys, r->n_keys * 8);
+      bh[j].keys_at = (int64_t)at;
+      at += r->n_keys * 8;
+    }
+  }
+  for (int j = 0; j < k; j++) { /* (the byte buffer may have moved while it grew) */
+    if (bh[j].bin_at >= 0) results[j].bin = g->h_bin + bh[j].bin_at;
+    if (bh[j].keys_at >= 0) results[j].keys = (const uint64_t*)(g->h_bin + bh[j].keys_at);
+  }
   return DG_OK;
 }

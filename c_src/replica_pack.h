@@ -57,4 +57,63 @@ int rp_cont_parse(const uint8_t* bin, uint64_t len, uint32_t* level, uint64_t* n
 /* the continuation whose pos | hash | bucket run stands at `base` (full: n = cap) */
 dg_merkle_cont rp_cont_at(uint64_t* base, uint32_t level, uint64_t n, uint64_t n_buckets);
 
+
+/* What one hop through dg_merkle_continue_home / dg_merkle_continues is given for its results,
+ * in page-locked words: C entries (pos | hash) and CB buckets for the next continuation, kcap
+ * keys.  From the incoming continuation (level, n entries) on a tree of `depth` over rows_n
+ * rows: a node form above the buckets expands to at most n << k children, k = min(levels,
+ * depth - level), truncated to max_sync; at the bucket level four pairs per bucket (at least
+ * 64), grown once to what the call reports; the keys are the first max_sync, at most every
+ * key of both sides and RP_CONT_SMALL_OUT.  A hop whose C exceeds RP_CONT_SMALL_OUT takes the
+ * general path. */
+#define RP_CONT_SMALL_OUT 65536 /* entries of an outgoing continuation / keys kept in host memory */
+typedef struct rp_cont_room {
+  uint64_t C, CB, kcap;
+} rp_cont_room;
+static inline uint64_t rp_u64min(uint64_t a, uint64_t b) { return a < b ? a : b; }
+static inline uint64_t rp_u64max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+static inline rp_cont_room rp_cont_room_for(uint32_t level, uint64_t n, uint32_t depth, uint32_t levels,
+                                            uint64_t max_sync, uint64_t rows_n) {
+  rp_cont_room r;
+  r.CB = rp_u64max(rp_u64min(n, max_sync), 1);
+  if (level < depth) {
+    const uint32_t k = levels < depth - level ? levels : depth - level;
+    r.C = rp_u64min(n << k, max_sync);
+  } else {
+    r.C = rp_u64max(4 * rp_u64min(n, max_sync), 64);
+  }
+  r.C = rp_u64max(r.C, 1);
+  r.kcap = rp_u64max(rp_u64min(rp_u64min(max_sync, rows_n + n + 1), RP_CONT_SMALL_OUT), 1);
+  return r;
+}
+/* The k hops' rooms carved from ONE block, end to end: hop j's words are pos [off[j], +C) |
+ * hash [+C, +2C) | bucket [+2C, +2C + CB) | keys [+2C + CB, +2C + CB + kcap), every region on
+ * an 8-byte word and none shared.  Returns the block's words (off[k] is written too). */
+static inline uint64_t rp_cont_carve(int k, const rp_cont_room* room, uint64_t* off) {
+  uint64_t w = 0;
+  for (int j = 0; j < k; j++) {
+    off[j] = w;
+    w += 2 * room[j].C + room[j].CB + room[j].kcap;
+  }
+  off[k] = w;
+  return w;
+}
+/* hop j's output continuation (empty: n = 0) and keys inside the block at `base` */
+static inline dg_merkle_cont rp_cont_room_out(uint64_t* base, uint64_t off, rp_cont_room r) {
+  dg_merkle_cont c;
+  c.level = 0;
+  c.reserved = 0;
+  c.pos = base + off;
+  c.hash = base + off + r.C;
+  c.n = 0;
+  c.cap = r.C;
+  c.bucket = base + off + 2 * r.C;
+  c.n_buckets = 0;
+  c.cap_buckets = r.CB;
+  return c;
+}
+static inline uint64_t* rp_cont_room_keys(uint64_t* base, uint64_t off, rp_cont_room r) {
+  return base + off + 2 * r.C + r.CB;
+}
+
 #endif /* DG_REPLICA_PACK_H */

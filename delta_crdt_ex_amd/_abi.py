@@ -131,6 +131,23 @@ class dg_merkle_cont(C.Structure):
     ]
 
 
+DG_CONT_BATCH_MAX = 64
+
+
+class dg_cont_hop(C.Structure):
+    """One hop of dg_merkle_continues: in, out, keys, cap from the caller; the rest written."""
+    _fields_ = [
+        ("in_", C.POINTER(dg_merkle_cont)),
+        ("out", C.POINTER(dg_merkle_cont)),
+        ("keys", VP),
+        ("cap", C.c_uint64),
+        ("n_keys", C.c_uint64),
+        ("n_total", C.c_uint64),
+        ("status", C.c_int),
+        ("rc", C.c_int),
+    ]
+
+
 DG_DIFF_OLD = 1
 DG_DIFF_NEW = 2
 
@@ -275,6 +292,8 @@ _SIGS = {
                                           C.POINTER(dg_merkle_cont), C.c_uint32, C.c_uint64,
                                           C.POINTER(dg_merkle_cont), P64, C.c_uint64, P64, P64,
                                           C.POINTER(C.c_int)]),
+    "dg_merkle_continues": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store), C.c_int,
+                                      C.POINTER(dg_cont_hop), C.c_uint32, C.c_uint64]),
     "dg_merkle_truncate": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_merkle_cont),
                                      C.c_uint64]),
     "dg_merkle_fold_roots": (C.c_int, [P64, C.c_uint32, P64]),

@@ -364,6 +364,7 @@ int dg_engine_destroy(dg_engine* e) {
   if (e->h_pub) hipHostFree(e->h_pub);
   if (e->started) hipFree(e->started);
   if (e->h_stage.p) hipHostFree(e->h_stage.p);
+  if (e->h_cont.p) hipHostFree(e->h_cont.p);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
   if (e->ev_in || e->ev_out) {  // a registered engine (creation got past the registry)
     if (e->ev_in) hipEventDestroy(e->ev_in);

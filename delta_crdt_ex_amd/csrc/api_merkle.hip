@@ -281,6 +281,119 @@ int dg_merkle_continue_home(dg_engine* e, const dg_merkle* t, const dg_store* s,
   return DG_OK;
 }
 
+static_assert(DG_CONT_BATCH_MAX == CONT_BATCH_MAX, "deltagpu.h's batch limit is the kernel's");
+static_assert(sizeof(ContHop) % sizeof(u64) == 0, "descriptors are whole words of the page-locked block");
+
+int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
+                        uint32_t levels, uint64_t max) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(t, "dg_merkle_continues"));
+  TRY(check_store(s, "dg_merkle_continues"));
+  if (k < 0 || k > CONT_BATCH_MAX) return fail(DG_E_INVAL, "dg_merkle_continues: k = %d hops (0 .. %d)", k, CONT_BATCH_MAX);
+  if ((k > 0 && !hops) || levels < 1) return fail(DG_E_INVAL, "dg_merkle_continues: bad arguments");
+  if (k == 0) return DG_OK;
+  // each hop's own checks, exactly dg_merkle_continue_home's
+  const u32 depth = t->depth;
+  std::vector<std::string> msgs(k);
+  auto hop_fail = [&](int j, int code, const char* fmt, unsigned long long a, unsigned long long b) {
+    char msg[256];
+    snprintf(msg, sizeof msg, fmt, a, b);
+    msgs[j] = msg;
+    hops[j].rc = code;
+  };
+  int slot[CONT_BATCH_MAX];  // workgroup -> hop
+  u32 nw = 0;
+  for (int j = 0; j < k; j++) {
+    dg_cont_hop& h = hops[j];
+    const dg_merkle_cont* in = h.in;
+    h.n_keys = h.n_total = 0;
+    h.status = 0;
+    h.rc = DG_OK;
+    if (!in || (h.cap && !h.keys)) { hop_fail(j, DG_E_INVAL, "bad arguments", 0, 0); continue; }
+    if (in->n && (!in->pos || !in->hash)) { hop_fail(j, DG_E_INVAL, "null input", 0, 0); continue; }
+    const bool leaf = in->level == depth + 1;
+    if (in->level > depth + 1) { hop_fail(j, DG_E_INVAL, "level %llu > depth %llu", in->level, depth); continue; }
+    if (leaf && in->n_buckets && !in->bucket) { hop_fail(j, DG_E_INVAL, "null buckets", 0, 0); continue; }
+    h.status = DG_CONT_DECLINED;
+    if (in->n > CS_IN || (leaf && in->n_buckets > CS_B)) continue;  // the general path
+    h.status = 0;
+    if (leaf ? in->n_buckets == 0 : in->n == 0) continue;  // {:ok, []}
+    if (!leaf && !h.out) { hop_fail(j, DG_E_INVAL, "null out", 0, 0); continue; }
+    slot[nw++] = j;
+  }
+  if (nw) {
+    TRY(set_device(e));
+    TRY(settle(e));
+    const size_t desc_words = sizeof(ContHop) / sizeof(u64);
+    TRY(ensure_cont(e, (size_t)CONT_BATCH_MAX * (desc_words + CONT_HDR_STRIDE)));
+    ContHop* hd = e->h_cont.as<ContHop>();
+    u64* hdr = e->h_cont.as<u64>() + (size_t)CONT_BATCH_MAX * desc_words;
+    for (u32 w = 0; w < nw; w++) {
+      const dg_cont_hop& h = hops[slot[w]];
+      const dg_merkle_cont* in = h.in;
+      const bool leaf = in->level == depth + 1;
+      ContHop d{};
+      d.level = in->level;
+      d.n = in->n;
+      d.nb = leaf ? in->n_buckets : 0;
+      d.ipos = in->pos;
+      d.ihash = in->hash;
+      d.ibucket = leaf ? in->bucket : nullptr;
+      if (h.out) {
+        d.opos = h.out->pos;
+        d.ohash = h.out->hash;
+        d.obucket = h.out->bucket;
+        d.ocap = h.out->pos && h.out->hash ? h.out->cap : 0;
+        d.ocap_b = h.out->bucket ? h.out->cap_buckets : 0;
+      }
+      d.keys = h.keys;
+      d.kcap = h.cap;
+      hd[w] = d;
+    }
+    ContBatchArgs p{};
+    p.t = merkle_of(t);
+    p.s = rows_of(s);
+    p.levels = levels;
+    p.max = max;
+    p.hops = hd;
+    p.hdr = hdr;
+    p.arrive = e->ticket + CONT_ARRIVE;
+    p.d_counts = e->d_counts;
+    p.h_pub = e->d_pub;
+    p.seq = ++e->pub_seq;
+    HIP_TRY(launch_cont_batch(p, nw, e->stream));
+    TRY(wait_published(e, p.seq));
+    for (u32 w = 0; w < nw; w++) {
+      const int j = slot[w];
+      dg_cont_hop& h = hops[j];
+      u64 r[CS_HDR];
+      memcpy(r, (const void*)(hdr + (size_t)w * CONT_HDR_STRIDE), sizeof r);
+      if (r[0] == CS_BAD) {
+        hop_fail(j, DG_E_INVAL, "a position or bucket outside the tree", 0, 0);
+      } else if (r[0] == CS_CAP) {
+        h.out->level = (u32)r[3];
+        h.out->n = r[4];
+        h.out->n_buckets = r[5];
+        hop_fail(j, DG_E_CAPACITY, "%llu entries / %llu buckets needed", r[4], r[5]);
+      } else if (r[0] == CS_OK) {
+        h.n_keys = std::min<u64>(r[1], h.cap);
+        h.n_total = r[1];
+      } else {
+        h.out->level = (u32)r[3];
+        h.out->n = r[1];
+        h.out->n_buckets = r[0] == CS_LEAF ? r[2] : 0;
+        h.status = 1;
+      }
+    }
+  }
+  for (int j = 0; j < k; j++)
+    if (hops[j].rc != DG_OK) {
+      fail(hops[j].rc, "dg_merkle_continues: hop %d: %s", j, msgs[j].c_str());
+      break;
+    }
+  return DG_OK;
+}
+
 int dg_merkle_truncate(dg_engine* e, const dg_merkle* t, dg_merkle_cont* cont, uint64_t max) {
   if (!e || !cont) return fail(DG_E_INVAL, "dg_merkle_truncate: null argument");
   TRY(check_merkle(t, "dg_merkle_truncate"));

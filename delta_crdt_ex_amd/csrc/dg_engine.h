@@ -78,6 +78,8 @@ struct dg_engine {
   int tree_rebuild = TREE_BY_SHARE;
   u64 tree_rebuild_div = 64;
   Buf h_stage;  // pinned staging of kernel descriptors
+  Buf h_cont;   // dg_merkle_continues: per hop its descriptor and its result header (pinned; the
+                // workgroups read the one and write the other in place)
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // hand-offs to the device's shared join stream
   // asynchronous calls since the last dg_engine_sync, replayed there (joins on the
   // two-pass kernels) when a single-pass join grid aborted for lack of residency
@@ -116,6 +118,8 @@ enum Ticket {
   MUT_ARRIVE = 9,   // dg_mutate_batch's count kernel: the last tile scans
   SPL_ARRIVE = 10,  // dg_join_delta's moved-rows copy: the last workgroup publishes
   KD_ERR = 11,      // dg_join_delta's tree input-error word (zero between calls)
+  CONT_ARRIVE = 12,  // dg_merkle_continues' hop kernel: every workgroup arrives, the last resets
+                     // the word and publishes (zero at creation and between launches)
 };
 constexpr int CONT_HOME = 18;  // h_pub words [18, 24): dg_merkle_continue_home's result header
 
@@ -267,6 +271,10 @@ inline int ensure_diff_bsum(dg_engine* e, u64 groups) {
 // pinned host staging (kernel descriptors, digit histograms)
 inline int ensure_stage(dg_engine* e, size_t bytes) {
   return grow(e, &e->h_stage, bytes, 1, 0, GROW_PINNED, "pinned staging of %zu bytes failed");
+}
+// dg_merkle_continues' block: k descriptors, then k result headers (u64 words)
+inline int ensure_cont(dg_engine* e, size_t words) {
+  return grow(e, &e->h_cont, words, sizeof(u64), 0, GROW_PINNED, "page-locked block of %llu continuation words failed");
 }
 
 // A scratch layout (dg_arena.h) in use: measured, the buffer grown to it (engine tmp with its

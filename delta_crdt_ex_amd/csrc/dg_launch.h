@@ -539,7 +539,7 @@ constexpr u64 DIFF_MISMATCH = 1ull << 44;
 hipError_t launch_merkle_diff(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb,
                               u64* out_keys, u64 cap, u64* scratch, u64* bsum, u64* bsum_zero, u64 nzero,
                               u64* d_count, hipStream_t st);
-// dg_merkle_continue_home's one-workgroup hop (merkle_cont.hip cont_small_kernel): limits,
+// dg_merkle_continue_home's one-workgroup hop (merkle_cont.hip cont_hop_kernel<false>): limits,
 // result kinds (home[0]) and arguments
 constexpr u32 CS_IN = 4096, CS_B = 512;  // entries / pairs in, buckets in (leaf form)
 constexpr u64 CS_OK = 0, CS_NODE = 1, CS_LEAF = 2, CS_CAP = 3, CS_BAD = 4;
@@ -561,6 +561,35 @@ struct ContSmallArgs {
   u64 seq;
 };
 hipError_t launch_cont_small(const ContSmallArgs& a, hipStream_t st);
+// dg_merkle_continues: k <= CONT_BATCH_MAX such hops, one workgroup each, in one launch
+// (cont_hop_kernel<true>).  Hop j's descriptor (what ContSmallArgs holds per call) and its
+// result header (CS_HDR words at hdr + j * CONT_HDR_STRIDE) are in page-locked host memory;
+// the last workgroup to arrive resets *arrive and publishes seq.
+constexpr int CONT_BATCH_MAX = 64;
+constexpr int CONT_HDR_STRIDE = 8;  // words between two hops' headers (a 64-byte line each)
+static_assert(CS_HDR <= CONT_HDR_STRIDE, "a header fits its slot");
+struct ContHop {
+  u32 level, pad;
+  u64 n, nb;
+  const u64 *ipos, *ihash, *ibucket;
+  u64 *opos, *ohash, *obucket;
+  u64 ocap, ocap_b;
+  u64* keys;
+  u64 kcap;
+};
+struct ContBatchArgs {
+  MerkleT t;
+  Rows s;
+  u32 levels;
+  u64 max;
+  const ContHop* hops;
+  u64* hdr;
+  u32* arrive;  // the engine's CONT_ARRIVE word: zero between launches
+  const u64* d_counts;
+  u64* h_pub;
+  u64 seq;
+};
+hipError_t launch_cont_batch(const ContBatchArgs& p, u32 k, hipStream_t st);
 // prepare_partial_diff: level L's positions and node hashes (2^L entries)
 hipError_t launch_cont_prepare(const MerkleT& t, u32 L, u64* opos, u64* ohash, hipStream_t st);
 // partial diff.  scratch: 2 * ceil(n / 256) u64.

@@ -5,8 +5,10 @@
 // Node-form continuations (positions + the sender's hashes at one level) are compared and
 // expanded `levels` levels down; at the bucket level the reply is a leaf-form continuation
 // (the sender's (key, leaf) pairs of the differing buckets), which the peer merges with its
-// own rows into keys.  cont_small_kernel does one whole hop of a small continuation in one
-// workgroup (dg_merkle_continue_home).
+// own rows into keys.  cont_hop_kernel does one whole hop of a small continuation in one
+// workgroup (dg_merkle_continue_home), or k such hops in k workgroups (dg_merkle_continues).
+#include <type_traits>
+
 #include "dg_home.h"
 #include "dg_launch.h"
 #include "dg_tree.h"
@@ -271,11 +273,67 @@ __device__ __forceinline__ u32 merge_regs(const BucketPairs& bp, const u64* pk, 
   return c;
 }
 
-__global__ __launch_bounds__(CSN) void cont_small_kernel(ContSmallArgs a, MerkleT t) {
+// dg_merkle_continues: the same hop by workgroup j of a grid of k <= CONT_BATCH_MAX, for hop j
+// of a batch (cont_hop_kernel<true>; <false> is the single hop above, instruction for
+// instruction).  The tree, the store, `levels` and `max` are the launch's; hop j's numbers
+// and pointers come from descriptor j (page-locked host memory, read through uniform loads),
+// its result header goes to slot j of hdr (page-locked too).  No workgroup waits for another.
+//
+// Completion, and why the host that has seen `seq` sees every workgroup's writes:
+//   (1) every thread of a workgroup, after its last write to host memory (outputs, keys, the
+//       header), executes __threadfence_system(): a release fence at system scope -- the
+//       thread's earlier writes are performed with respect to the host before anything the
+//       thread, or a thread that synchronizes with it, does afterwards;
+//   (2) the workgroup barrier orders all its threads' fences before lane 0's add to the
+//       arrival word (agent scope: the adds of one launch are a total order on one word);
+//   (3) the workgroup whose add returns gridDim.x - 1 has read, through the chain of
+//       read-modify-writes, the adds of all the others, each of which follows that
+//       workgroup's fences (2); its own __threadfence_system() after the add (acquire and
+//       release) therefore orders every workgroup's host writes before its store of `seq`
+//       (publish_counts: another system fence, then a system-scope release store);
+//   (4) the host reads `seq` and then fences (wait_published), so it reads the headers and
+//       the outputs after (3).
+// The arrival word is zero between launches: the last workgroup, which alone knows that every
+// add has happened, stores 0 before it publishes, and a launch that did not start added nothing.
+//
+// The kernel is the template and its LDS stays function-local: with the arrays gathered into
+// one namespace-scope block, or with the single hop's arguments copied rather than bound by
+// reference (hop_args), the single hop's code moved (188 VGPRs, another schedule); as it
+// stands <false> is the former cont_small_kernel in every instruction and .amdhsa line.
+
+// the hop's arguments: the call's own, or those of this workgroup's descriptor
+__device__ __forceinline__ const ContSmallArgs& hop_args(const ContSmallArgs& p) { return p; }
+__device__ __forceinline__ ContSmallArgs hop_args(const ContBatchArgs& p) {
+  ContSmallArgs a;
+  const ContHop& d = p.hops[blockIdx.x];
+  a.s = p.s;
+  a.level = d.level;
+  a.levels = p.levels;
+  a.max = p.max;
+  a.ipos = d.ipos;
+  a.ihash = d.ihash;
+  a.ibucket = d.ibucket;
+  a.n = d.n;
+  a.nb = d.nb;
+  a.opos = d.opos;
+  a.ohash = d.ohash;
+  a.obucket = d.obucket;
+  a.ocap = d.ocap;
+  a.ocap_b = d.ocap_b;
+  a.keys = d.keys;
+  a.kcap = d.kcap;
+  a.home = p.hdr + (u64)blockIdx.x * CONT_HDR_STRIDE;
+  return a;
+}
+
+template <bool BATCH>
+__global__ __launch_bounds__(CSN) void cont_hop_kernel(
+    typename std::conditional<BATCH, ContBatchArgs, ContSmallArgs>::type p, MerkleT t) {
   __shared__ u64 s_dpos[CS_IN];
   __shared__ u64 s_pk[CS_IN], s_ph[CS_IN];  // leaf form in: the peer's pairs; node form: bucket rows
   __shared__ u32 s_wave[CSN / WAVE + 1];
   __shared__ u32 s_bad;
+  const ContSmallArgs& a = hop_args(p);
   const int tid = threadIdx.x;
   const u32 depth = t.depth, L = a.level;
   u64 h[CS_HDR] = {0, 0, 0, 0, 0, 0};  // the result header (every thread's copy is the same)
@@ -446,7 +504,23 @@ __global__ __launch_bounds__(CSN) void cont_small_kernel(ContSmallArgs a, Merkle
     for (int i = 0; i < CS_HDR; i++) v = i == tid ? h[i] : v;
     a.home[tid] = v;
   }
-  publish_counts(a.d_counts, a.h_pub, a.seq);
+  if constexpr (BATCH) {
+    __threadfence_system();  // (1)
+    __syncthreads();         // (2): also past every read of s_bad
+    if (tid == 0) {
+      const u32 arrived = __hip_atomic_fetch_add(p.arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = arrived == gridDim.x - 1;
+      if (last) __hip_atomic_store(p.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s_bad = last ? 1u : 0u;
+    }
+    __syncthreads();
+    if (s_bad) {
+      __threadfence_system();  // (3)
+      publish_counts(p.d_counts, p.h_pub, p.seq);
+    }
+  } else {
+    publish_counts(a.d_counts, a.h_pub, a.seq);
+  }
 }
 
 }  // namespace
@@ -457,7 +531,12 @@ hipError_t launch_cont_prepare(const MerkleT& t, u32 L, u64* opos, u64* ohash, h
 }
 
 hipError_t launch_cont_small(const ContSmallArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(cont_small_kernel, dim3(1), dim3(CSN), 0, st, a, a.t);
+  hipLaunchKernelGGL(cont_hop_kernel<false>, dim3(1), dim3(CSN), 0, st, a, a.t);
+  return hipGetLastError();
+}
+
+hipError_t launch_cont_batch(const ContBatchArgs& p, u32 k, hipStream_t st) {
+  hipLaunchKernelGGL(cont_hop_kernel<true>, dim3(k), dim3(CSN), 0, st, p, p.t);
   return hipGetLastError();
 }
 

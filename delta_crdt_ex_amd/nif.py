@@ -23,6 +23,8 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
     merkle_prepare(state, version, levels)          -> ("continue", bytes)
     merkle_continue(state, version, cont, levels, max_sync_size | "infinite")
                                                     -> ("continue", bytes) | ("ok", keys)
+    merkle_continue_batch(state, version, [cont, ...], levels, max_sync_size | "infinite")
+                                                    -> ("ok", [("continue", bytes) | ("ok", keys), ...])
     sweep(engine)                                   -> ("ok", {"values": (before, after),
                                                                "keys": (before, after)})
     resolve_keys(engine, keys)                      -> keys
@@ -78,6 +80,11 @@ class dgr_taken(C.Structure):
                 ("rows", dg_store)]
 
 
+class dgr_cont_result(C.Structure):
+    _fields_ = [("rc", C.c_int), ("status", C.c_int), ("bin", C.c_void_p), ("len", C.c_uint64),
+                ("keys", C.c_void_p), ("n_keys", C.c_uint64)]
+
+
 VP, U64, I32 = C.c_void_p, C.c_uint64, C.c_int
 PU64 = C.POINTER(C.c_uint64)
 _SIGS = {
@@ -118,6 +125,8 @@ _SIGS = {
     "dgr_merkle_prepare": (I32, [VP, U64, C.c_uint32, C.POINTER(VP), PU64]),
     "dgr_merkle_continue": (I32, [VP, U64, C.c_char_p, U64, C.c_uint32, U64, C.POINTER(I32),
                                   C.POINTER(VP), PU64, C.POINTER(VP), PU64]),
+    "dgr_merkle_continue_batch": (I32, [VP, U64, I32, C.POINTER(C.c_char_p), PU64, C.c_uint32, U64,
+                                        C.POINTER(dgr_cont_result)]),
 }
 
 _lib = None
@@ -634,6 +643,41 @@ def merkle_continue(state: State, version: int, cont: bytes, levels: int, max_sy
     return ("ok", [_key_term(eng, kid) for kid in _arr(pk, nk.value, np.uint64)])
 
 
+CONT_BATCH_MAX = _abi.DG_CONT_BATCH_MAX  # messages per dgr_merkle_continue_batch call
+
+
+def merkle_continue_batch(state: State, version: int, conts, levels: int, max_sync):
+    """merkle_continue for k pending {:diff, %Diff{continuation: ...}} messages as one call per
+    64 (dgr_merkle_continue_batch: one launch and one wait for the messages within the
+    one-workgroup limits): ("ok", [r_0, ...]), r_j what merkle_continue(state, version,
+    conts[j], levels, max_sync) is.  All answers are computed against the state as it is
+    now.  A stale version fails the whole call."""
+    eng = state.engine
+    rc = eng.refresh_terms()
+    if rc:
+        return _err(rc)
+    mx = U64_MAX if max_sync == "infinite" else int(max_sync)
+    conts = list(conts)
+    out = []
+    for c0 in range(0, len(conts), CONT_BATCH_MAX):
+        chunk = conts[c0:c0 + CONT_BATCH_MAX]
+        k = len(chunk)
+        bins = (C.c_char_p * k)(*chunk)
+        lens = (C.c_uint64 * k)(*[len(c) for c in chunk])
+        res = (dgr_cont_result * k)()
+        rc = eng.lib.dgr_merkle_continue_batch(state.ptr, version, k, bins, lens, levels, mx, res)
+        if rc:
+            return _err(rc)
+        for r in res:
+            if r.rc:
+                out.append(_err(r.rc))
+            elif r.status == 1:
+                out.append(("continue", C.string_at(r.bin, r.len)))
+            else:
+                out.append(("ok", [_key_term(eng, kid) for kid in _arr(r.keys, r.n_keys, np.uint64)]))
+    return ("ok", out)
+
+
 def sweep(engine: Engine, keys: bool = True):
     return engine.sweep(keys=keys)
 
@@ -663,5 +707,5 @@ def resolve_keys(engine: Engine, keys):
 __all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "join_delta_diffs",
            "mutate_batch_diffs", "join_deltas", "join_deltas_diffs", "classify_diffs", "read", "take",
            "take_batch",
-           "merkle_build", "merkle_prepare", "merkle_continue", "sweep", "resolve_keys", "key_placeholder",
+           "merkle_build", "merkle_prepare", "merkle_continue", "merkle_continue_batch", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

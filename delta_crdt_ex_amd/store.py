@@ -1076,6 +1076,66 @@ class Engine:
             return ("continue", out)
         return ("ok", keys[: nk.value], int(tot.value))
 
+    def merkle_continues(self, tree: MerkleTree, conts, levels: int = 8, max_entries: int | None = None,
+                         caps=None, retry: bool = True):
+        """dg_merkle_continues: the hops of k <= 64 pending continuations (k neighbours'
+        messages) against ONE tree in one launch with one host wait.  A list whose element j is
+        what merkle_continue_home(tree, conts[j], levels, max_entries) returns, or ("error", code)
+        where that call would raise (one hop's error leaves the others' results).  `caps`: per hop the (entries, buckets)
+        its output is first given (default: merkle_continue_home's); a hop that reports
+        DG_E_CAPACITY is retried, alone with the other such hops, at the sizes it reported
+        (retry=False: its element is ("capacity", entries, buckets), the sizes needed)."""
+        self._order()
+        conts = list(conts)
+        k = len(conts)
+        s = tree.store
+        mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
+        t, ss = tree.abi(), s.abi()
+        hops = (_abi.dg_cont_hop * max(k, 1))()
+        cins = [c.abi() for c in conts]
+        sizes, outs, cos, keys = [], [None] * k, [None] * k, []
+        for j, c in enumerate(conts):
+            oc, ob = 4 * max(c.n, 1), max(c.n, 1)
+            if max_entries is not None:
+                oc = min(oc, max(int(max_entries), 1))
+            sizes.append(tuple(caps[j]) if caps is not None and caps[j] is not None else (oc, ob))
+            cap = max(c.n, 1) + s.n
+            keys.append(torch.empty(max(int(cap), 1), dtype=_I64, device=self.device))
+            hops[j].in_ = C.pointer(cins[j])
+            hops[j].keys = keys[j].data_ptr()
+            hops[j].cap = int(cap)
+        todo = list(range(k))
+        res = [None] * k
+        for attempt in range(3):
+            batch = (_abi.dg_cont_hop * max(len(todo), 1))()
+            for i, j in enumerate(todo):
+                outs[j] = MerkleCont.empty(sizes[j][0], sizes[j][1], self.device)
+                cos[j] = outs[j].abi()
+                hops[j].out = C.pointer(cos[j])
+                batch[i] = hops[j]
+            check(self.lib.dg_merkle_continues(self.h, C.byref(t), C.byref(ss), len(todo), batch, levels, mx))
+            again = []
+            for i, j in enumerate(todo):
+                h = batch[i]
+                if h.rc == _abi.DG_E_CAPACITY and not retry:
+                    res[j] = ("capacity", int(cos[j].n), int(cos[j].n_buckets))
+                elif h.rc == _abi.DG_E_CAPACITY and attempt < 2:
+                    sizes[j] = (max(int(cos[j].n), sizes[j][0]), max(int(cos[j].n_buckets), sizes[j][1]))
+                    again.append(j)
+                elif h.rc != _abi.DG_OK:
+                    res[j] = ("error", h.rc)
+                elif h.status == _abi.DG_CONT_DECLINED:
+                    res[j] = ("declined",)
+                elif h.status == 1:
+                    outs[j]._set(cos[j])
+                    res[j] = ("continue", outs[j])
+                else:
+                    res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total))
+            todo = again
+            if not todo:
+                break
+        return res
+
     def merkle_truncate(self, tree: MerkleTree, cont: MerkleCont, max_entries: int) -> MerkleCont:
         """MerkleMap.truncate_diff(cont, max_sync_size) (causal_crdt.ex:98,212-214)."""
         c = cont.abi()

@@ -660,6 +660,33 @@ int dg_merkle_continue_home(dg_engine* e, const dg_merkle* t, const dg_store* s,
                             uint32_t levels, uint64_t max, dg_merkle_cont* out, uint64_t* keys, uint64_t cap,
                             uint64_t* n_keys, uint64_t* n_total, int* status);
 
+/* k such hops (k pending {:diff, %Diff{continuation: ...}} messages of k neighbours) against
+ * ONE tree and store in ONE launch with ONE host wait: hop j is done by workgroup j of the
+ * grid, and `levels` and `max` are the call's.  Per hop, `status`, `rc`, out->{level, n,
+ * n_buckets}, `keys`, `n_keys` and `n_total` are what dg_merkle_continue_home returns for
+ * that hop alone: DG_CONT_DECLINED over the limits (nothing done for it), {:ok, []} for an
+ * empty input (no workgroup), DG_E_CAPACITY with the sizes needed in `out`, DG_E_INVAL for
+ * a position or bucket outside the tree or for a bad argument of the hop (`out` may be NULL
+ * for a leaf form, `keys` with cap 0).  One hop's error or decline does not touch the others.
+ * The call itself returns DG_E_INVAL before any launch for k < 0, k > DG_CONT_BATCH_MAX,
+ * null `hops` with k > 0, levels < 1 or a bad tree or store; otherwise DG_OK, with
+ * dg_last_error naming the first hop whose rc is not DG_OK.  With k == 0, or no hop that
+ * needs a workgroup, nothing is launched or waited for.
+ * The hops' outputs (out->pos / hash / bucket, keys) MUST NOT overlap one another or any
+ * hop's input: the workgroups write them concurrently, and the call does not check. */
+#define DG_CONT_BATCH_MAX 64
+typedef struct {
+  const dg_merkle_cont* in; /* as dg_merkle_continue_home's */
+  dg_merkle_cont* out;
+  uint64_t* keys;           /* {:ok, keys}: the first cap */
+  uint64_t cap;
+  uint64_t n_keys, n_total; /* written by the call, as are status and rc */
+  int status;
+  int rc;
+} dg_cont_hop;
+int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
+                        uint32_t levels, uint64_t max);
+
 /* MerkleMap.truncate_diff(cont, max) (causal_crdt.ex:98,212-214): keep the first `max`
  * entries of a node-form continuation, or the pairs of the first `max` buckets of a
  * leaf-form one (`t`: the tree that produced it; a leaf form needs one device
