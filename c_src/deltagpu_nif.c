@@ -51,6 +51,10 @@
  *                                                      -> {:ok, [{:continue, cont} | {:ok, keys}, ...]}
  *        (:96-105; `max` is max_sync_size or :infinite, :98,105,206-214; a key this node
  *        never interned comes back as {:"$dg_key", id})
+ *   merkle_continue_take_batch(state, version, [cont, ...], [want, ...], levels, max)
+ *                                                      -> {:ok, [{:continue, cont} | {:ok, keys}
+ *                                                                | {:ok, keys, value_map}, ...]}
+ *        (merkle_continue_batch with Map.take(value, keys), :324-335, where `want` is true)
  *   resolve_keys(engine, keys)                         -> keys (placeholders -> terms)
  *   (a continuation is an opaque binary)
  */
@@ -1238,6 +1242,73 @@ out:
   return r;
 }
 
+/* merkle_continue_take_batch(state, version, [cont, ...], [want, ...], levels, max_sync_size | :infinite)
+ *   -> {:ok, [{:continue, cont} | {:ok, keys} | {:ok, keys, value_map}, ...]}: merkle_continue_batch/5
+ * that also answers send_diff (:324-335) for the messages whose `want` is true (the originator of
+ * the sync: diff.originator != diff.to): where merkle_continue/5 gives {:ok, keys} with keys, the
+ * element is {:ok, keys, value_map}, value_map what take/3 of those keys gives.  One
+ * dgr_merkle_continue_take_batch per 64 messages: the rows come out of the hops' own launch. */
+static ERL_NIF_TERM merkle_continue_take_batch_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  state_res* s;
+  uint64_t version;
+  unsigned total, n_want, levels;
+  ErlNifUInt64 max_sync = UINT64_MAX;
+  if (!get_state(env, argv[0], argv[1], &s, &version) || !enif_get_list_length(env, argv[2], &total) ||
+      !enif_get_list_length(env, argv[3], &n_want) || n_want != total || !enif_get_uint(env, argv[4], &levels) ||
+      (!enif_is_identical(argv[5], A_INFINITE) && !enif_get_uint64(env, argv[5], &max_sync)))
+    return enif_make_badarg(env);
+  engine_res* g = s->eng;
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  const uint8_t* bins[DG_CONT_BATCH_MAX];
+  uint64_t lens[DG_CONT_BATCH_MAX];
+  uint8_t want[DG_CONT_BATCH_MAX];
+  dgr_cont_result res[DG_CONT_BATCH_MAX];
+  dgr_hop_rows taken[DG_CONT_BATCH_MAX];
+  const ERL_NIF_TERM a_true = enif_make_atom(env, "true");
+  ERL_NIF_TERM* out = (ERL_NIF_TERM*)enif_alloc((total ? total : 1) * sizeof *out);
+  ERL_NIF_TERM r, h, w, t = argv[2], tw = argv[3];
+  unsigned done = 0;
+  if (!out) TRY(DG_E_NOMEM);
+  TRY(refresh_terms(g));
+  while (done < total) {
+    int k = 0;
+    while (k < DG_CONT_BATCH_MAX && enif_get_list_cell(env, t, &h, &t) && enif_get_list_cell(env, tw, &w, &tw)) {
+      ErlNifBinary in;
+      if (!enif_inspect_binary(env, h, &in)) TRY(DG_E_INVAL);
+      bins[k] = in.data;
+      lens[k] = in.size;
+      want[k] = enif_is_identical(w, a_true) ? 1 : 0;
+      k++;
+    }
+    if (k == 0) TRY(DG_E_INVAL);
+    TRY(dgr_merkle_continue_take_batch(s->s, version, k, bins, lens, want, levels, max_sync, res, taken));
+    for (int j = 0; j < k; j++) {
+      if (res[j].rc) {
+        out[done + j] = error_term(env, res[j].rc);
+      } else if (res[j].status == 1) {
+        out[done + j] = enif_make_tuple2(env, A_CONTINUE, bytes_term(env, res[j].bin, res[j].len));
+      } else {
+        ERL_NIF_TERM l = enif_make_list(env, 0), values = A_NIL;
+        for (uint64_t i = res[j].n_keys; i-- > 0;) l = enif_make_list_cell(env, key_term(env, g, res[j].keys[i]), l);
+        if (want[j] && res[j].n_keys) {
+          TRY(unmarshal_host_rows(env, g, &taken[j].rows, &values));
+          out[done + j] = enif_make_tuple3(env, A_OK, l, values);
+        } else {
+          out[done + j] = enif_make_tuple2(env, A_OK, l);
+        }
+      }
+    }
+    done += (unsigned)k;
+  }
+out:
+  r = rc ? error_term(env, rc) : enif_make_tuple2(env, A_OK, enif_make_list_from_array(env, out, total));
+  if (out) enif_free(out);
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
 /* resolve_keys(engine, keys) -> keys: placeholders of keys this node knows -> their terms
  * (the others stay placeholders) */
 static ERL_NIF_TERM resolve_keys_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
@@ -1298,6 +1369,7 @@ static ErlNifFunc funcs[] = {
     {"merkle_prepare", 3, merkle_prepare_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_continue", 5, merkle_continue_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"merkle_continue_batch", 5, merkle_continue_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"merkle_continue_take_batch", 6, merkle_continue_take_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"resolve_keys", 2, resolve_keys_nif, 0},
     {"sweep", 1, sweep_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };

@@ -118,6 +118,8 @@ int dgr_engine_close(dgr_engine* g) {
   dg_host_free(e, g->h_ckeys);
   dg_host_free(e, g->h_cstage);
   dg_host_free(e, g->h_bstage);
+  dg_host_free(e, g->h_tstage);
+  dg_host_free(e, g->h_tfall);
   free(g->h_bin);
   free(g->sw_stores);
   free(g->b_rows); /* (and b_ctx, b_keys, b_nk, b_unsorted behind it) */

@@ -249,6 +249,28 @@ typedef struct dgr_cont_result {
 int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
                               const uint64_t* lens, uint32_t levels, uint64_t max_sync, dgr_cont_result* results);
 
+/* dgr_merkle_continue_batch that also answers send_diff on the originator of a sync
+ * (causal_crdt.ex:104-105, :324-335): results[j] is byte for byte dgr_merkle_continue_batch's, and
+ * wherever want_rows[j] != 0 and the answer is {:ok, keys} with n_keys > 0, taken[j] is what
+ * dgr_take(s, version, results[j].keys, results[j].n_keys) returns, with offs (n_keys + 1 entries):
+ * rows [offs[i], offs[i + 1]) are keys[i]'s.  Otherwise taken[j] is empty (rows.n == 0, offs NULL).
+ * The hops of the launch get their rows out of the same launch and wait
+ * (dg_merkle_continues_take), into min(rows_n, 4 * min(kcap, 4096) + 64) rows of page-locked room
+ * each (replica_pack.h rp_take_carve).  Every other hop that wants rows -- one answered by the
+ * general calls, one whose rows did not fit -- is answered as in dgr_merkle_continue_batch and
+ * its rows are taken afterwards: by ONE take for all such hops (dg_take_keysets; dgr_take's keyed
+ * gather when there is one).  A lone hop goes to the single call, as in dgr_merkle_continue_batch,
+ * and its rows are taken afterwards (DGR_TAKE_LONE=1: a lone leaf form that wants rows goes through
+ * the launch at k = 1; DESIGN 4.16 has both measured).  Host views, valid until the next call on
+ * the engine; one version check. */
+typedef struct dgr_hop_rows {
+  dg_store rows;
+  const uint64_t* offs;
+} dgr_hop_rows;
+int dgr_merkle_continue_take_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
+                                   const uint64_t* lens, const uint8_t* want_rows, uint32_t levels,
+                                   uint64_t max_sync, dgr_cont_result* results, dgr_hop_rows* taken);
+
 #ifdef __cplusplus
 }
 #endif

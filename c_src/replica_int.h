@@ -78,6 +78,10 @@ struct dgr_engine {
   /* dgr_merkle_continue_batch: the k hops' outputs (page-locked, replica_pack.h rp_cont_carve) */
   uint64_t* h_bstage;
   uint64_t h_bstage_cap;
+  /* dgr_merkle_continue_take_batch: the hops' rows and offsets out of the launch (page-locked,
+   * rp_take_carve), and those of the hops that took theirs through dgr_take_batch, per hop */
+  uint64_t *h_tstage, *h_tfall;
+  uint64_t h_tstage_cap, h_tfall_cap;
   /* dgr_sweep: the live states' stores as one host array */
   dg_store* sw_stores;
   uint64_t sw_cap;
@@ -108,5 +112,8 @@ int ri_grow_ctx(dgr_engine* g, dg_context* c, uint64_t n);
 int ri_grow_back(dgr_engine* g, uint64_t S, uint64_t C); /* the return block */
 int ri_grow_batch(dgr_engine* g, uint64_t k);            /* the b_* arrays */
 void ri_free_tree(dgr_state* s);
+/* dgr_take / dgr_take_batch behind their argument and version checks (replica_take.c) */
+int ri_take(dgr_state* s, const uint64_t* keys, uint64_t n_keys, dg_store* out);
+int ri_take_batch(dgr_state* s, int k, const uint64_t* const* keys, const uint64_t* n_keys, dgr_taken* out);
 
 #endif /* DG_REPLICA_INT_H */

@@ -223,7 +223,7 @@ typedef struct batch_hop {
 
 static int continue_hops(dgr_state* s, const batch_hop* bh, const int* idx, int m, uint64_t* block,
                          const rp_cont_room* room, const uint64_t* off, uint32_t levels, uint64_t max_sync,
-                         dg_merkle_cont* cin, dg_merkle_cont* cout, dg_cont_hop* hops) {
+                         dg_merkle_cont* cin, dg_merkle_cont* cout, dg_cont_hop* hops, dg_cont_take* const* takes) {
   dgr_engine* g = s->g;
   for (int i = 0; i < m; i++) {
     const batch_hop* b = &bh[idx[i]];
@@ -235,11 +235,26 @@ static int continue_hops(dgr_state* s, const batch_hop* bh, const int* idx, int 
     hops[i].keys = room[i].kcap ? rp_cont_room_keys(block, off[i], room[i]) : NULL;
     hops[i].cap = room[i].kcap;
   }
-  return dg_merkle_continues(g->e, &s->tree, &s->rows, m, hops, levels, max_sync);
+  return dg_merkle_continues_take(g->e, &s->tree, &s->rows, m, hops, takes, levels, max_sync);
 }
 
-int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
-                              const uint64_t* lens, uint32_t levels, uint64_t max_sync, dgr_cont_result* results) {
+/* A lone leaf-form hop that wants rows: 1 = through the take launch at k = 1, 0 = the single hop
+ * and then the take.  DGR_TAKE_LONE=0 / 1 overrides the default (A/B). */
+#define TAKE_LONE_DEFAULT 0
+static int take_lone(void) {
+  static int lone = -1;
+  if (lone < 0) {
+    const char* v = getenv("DGR_TAKE_LONE");
+    lone = v ? atoi(v) != 0 : TAKE_LONE_DEFAULT;
+  }
+  return lone;
+}
+
+/* dgr_merkle_continue_batch (want == NULL), and dgr_merkle_continue_take_batch's answers with the
+ * rows that came out of the launch: taken[j].offs != NULL where hop j's did */
+static int continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins, const uint64_t* lens,
+                          const uint8_t* want, uint32_t levels, uint64_t max_sync, dgr_cont_result* results,
+                          dgr_hop_rows* taken) {
   if (!s || k < 0 || k > DG_CONT_BATCH_MAX || (k && (!bins || !lens || !results)) || levels < 1) return DG_E_INVAL;
   for (int j = 0; j < k; j++)
     if (!bins[j]) return DG_E_INVAL;
@@ -268,7 +283,9 @@ int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8
     room[m] = r;
     idx[m++] = j;
   }
-  if (m == 1) { /* one hop for the launch: the single call's own launch is 5-6 us shorter (bench_hops) */
+  /* one hop for the launch: the single call's own launch is 5-6 us shorter (bench_hops); a lone leaf
+   * form whose rows are wanted goes the way take_lone() says (bench_hop_take) */
+  if (m == 1 && !(take_lone() && want && want[idx[0]] && bh[idx[0]].level == depth + 1)) {
     bh[idx[0]].general = 1;
     m = 0;
   }
@@ -283,7 +300,30 @@ int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8
       if (2 * b->n + b->nb) memcpy(g->h_msg + b->moff, bins[idx[i]] + RP_CONT_HEAD, (2 * b->n + b->nb) * 8);
     }
     TRY(ri_grow(g, &g->h_bstage, NULL, &g->h_bstage_cap, umax(rp_cont_carve(m, room, off), 1)));
-    TRY(continue_hops(s, bh, idx, m, g->h_bstage, room, off, levels, max_sync, cin, cout, hops));
+    /* the rows of the leaf forms that want them, out of the same launch */
+    dg_cont_take take[DG_CONT_BATCH_MAX];
+    dg_cont_take* takes[DG_CONT_BATCH_MAX];
+    int n_takes = 0;
+    for (int i = 0; i < m; i++) takes[i] = NULL;
+    if (want) {
+      rp_take_room troom[DG_CONT_BATCH_MAX];
+      uint64_t toff[DG_CONT_BATCH_MAX + 1];
+      for (int i = 0; i < m; i++) {
+        const int on = want[idx[i]] && bh[idx[i]].level == depth + 1;
+        troom[i] = rp_take_room_for(on ? room[i].kcap : 0, on ? s->rows.n : 0);
+        n_takes += on;
+      }
+      if (n_takes) TRY(ri_grow(g, &g->h_tstage, NULL, &g->h_tstage_cap, umax(rp_take_carve(m, troom, toff), 1)));
+      for (int i = 0; i < m; i++) {
+        if (!(want[idx[i]] && bh[idx[i]].level == depth + 1)) continue;
+        memset(&take[i], 0, sizeof take[i]);
+        take[i].rows = rp_take_room_rows(g->h_tstage, toff[i], troom[i]);
+        take[i].offs = rp_take_room_offs(g->h_tstage, toff[i], troom[i]);
+        takes[i] = &take[i];
+      }
+    }
+    TRY(continue_hops(s, bh, idx, m, g->h_bstage, room, off, levels, max_sync, cin, cout, hops,
+                      n_takes ? takes : NULL));
     /* DG_E_CAPACITY: one retry at the sizes reported, with only the hops that reported it (their
      * outputs staged where a single hop's are: a node form's answer has no keys) */
     int ridx[DG_CONT_BATCH_MAX], rpos[DG_CONT_BATCH_MAX], rm = 0;
@@ -304,10 +344,11 @@ int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8
       dg_cont_hop rhops[DG_CONT_BATCH_MAX];
       uint64_t roff[DG_CONT_BATCH_MAX + 1];
       TRY(ri_grow(g, &g->h_cstage, NULL, &g->h_cstage_cap, umax(rp_cont_carve(rm, rroom, roff), 1)));
-      TRY(continue_hops(s, bh, ridx, rm, g->h_cstage, rroom, roff, levels, max_sync, rin, rout, rhops));
+      TRY(continue_hops(s, bh, ridx, rm, g->h_cstage, rroom, roff, levels, max_sync, rin, rout, rhops, NULL));
       for (int i = 0; i < rm; i++) {
         hops[rpos[i]] = rhops[i];
         cout[rpos[i]] = rout[i];
+        takes[rpos[i]] = NULL; /* retried without a take (only node forms report capacity) */
       }
     }
     for (int i = 0; i < m; i++) {
@@ -325,6 +366,10 @@ int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8
         }
         r->keys = hops[i].keys;
         r->n_keys = hops[i].n_keys;
+        if (takes[i] && take[i].rc == DG_OK && r->n_keys) {
+          taken[j].rows = take[i].rows;
+          taken[j].offs = take[i].offs;
+        }
       } else {
         const uint8_t* p;
         r->status = 1;
@@ -357,6 +402,80 @@ int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8
   for (int j = 0; j < k; j++) { /* (the byte buffer may have moved while it grew) */
     if (bh[j].bin_at >= 0) results[j].bin = g->h_bin + bh[j].bin_at;
     if (bh[j].keys_at >= 0) results[j].keys = (const uint64_t*)(g->h_bin + bh[j].keys_at);
+  }
+  return DG_OK;
+}
+
+int dgr_merkle_continue_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
+                              const uint64_t* lens, uint32_t levels, uint64_t max_sync, dgr_cont_result* results) {
+  return continue_batch(s, version, k, bins, lens, NULL, levels, max_sync, results, NULL);
+}
+
+int dgr_merkle_continue_take_batch(dgr_state* s, uint64_t version, int k, const uint8_t* const* bins,
+                                   const uint64_t* lens, const uint8_t* want_rows, uint32_t levels,
+                                   uint64_t max_sync, dgr_cont_result* results, dgr_hop_rows* taken) {
+  if (k > 0 && (!want_rows || !taken)) return DG_E_INVAL;
+  if (k > 0 && k <= DG_CONT_BATCH_MAX) memset(taken, 0, (size_t)k * sizeof *taken);
+  TRY(continue_batch(s, version, k, bins, lens, want_rows, levels, max_sync, results, taken));
+  /* the hops whose rows did not come out of the launch: ONE dgr_take_batch on their keys (host
+   * views that it leaves alone), then each hop's rows and offsets laid out on their own */
+  const uint64_t* keys[DG_CONT_BATCH_MAX];
+  uint64_t nk[DG_CONT_BATCH_MAX];
+  int who[DG_CONT_BATCH_MAX], f = 0;
+  for (int j = 0; j < k; j++) {
+    const dgr_cont_result* r = &results[j];
+    if (!want_rows[j] || r->rc != DG_OK || r->status != 0 || !r->n_keys || taken[j].offs) continue;
+    keys[f] = r->keys;
+    nk[f] = r->n_keys;
+    who[f++] = j;
+  }
+  if (!f) return DG_OK;
+  dgr_engine* g = s->g;
+  if (f == 1) { /* one hop: dgr_take's keyed gather (no union to sort), its rows as they came home */
+    dg_store v;
+    TRY(ri_take(s, keys[0], nk[0], &v));
+    TRY(ri_grow(g, &g->h_tfall, NULL, &g->h_tfall_cap, nk[0] + 1));
+    uint64_t r = 0;
+    for (uint64_t i = 0; i < nk[0]; i++) { /* keys and rows ascend together */
+      g->h_tfall[i] = r;
+      while (r < v.n && v.key[r] == keys[0][i]) r++;
+    }
+    g->h_tfall[nk[0]] = r;
+    if (r != v.n) return DG_E_INVAL;
+    taken[who[0]].rows = v;
+    taken[who[0]].offs = g->h_tfall;
+    return DG_OK;
+  }
+  dgr_taken u;
+  TRY(ri_take_batch(s, f, keys, nk, &u)); /* (the version was checked above, once) */
+  uint64_t n[DG_CONT_BATCH_MAX], at[DG_CONT_BATCH_MAX], words = 0;
+  for (int i = 0; i < f; i++) {
+    n[i] = 0;
+    for (uint64_t q = 0; q < u.n_keys; q++)
+      if (u.masks[q] >> i & 1) n[i] += u.offs[q + 1] - u.offs[q];
+    at[i] = words;
+    words += rows_words(n[i]) + even(nk[i] + 1);
+  }
+  TRY(ri_grow(g, &g->h_tfall, NULL, &g->h_tfall_cap, umax(words, 1)));
+  for (int i = 0; i < f; i++) {
+    dg_store v = rp_rows(g->h_tfall + at[i], even(n[i]), 0, umax(n[i], 1));
+    uint64_t* offs = g->h_tfall + at[i] + rows_words(n[i]);
+    uint64_t t = 0;
+    for (uint64_t q = 0; q < u.n_keys; q++) { /* the union is ascending, as the hop's keys are */
+      if (!(u.masks[q] >> i & 1)) continue;
+      const uint64_t a = u.offs[q], c = u.offs[q + 1] - a;
+      offs[t++] = v.n;
+      memcpy(v.key + v.n, u.rows.key + a, c * 8);
+      memcpy(v.val + v.n, u.rows.val + a, c * 8);
+      memcpy(v.ts + v.n, u.rows.ts + a, c * 8);
+      memcpy(v.node + v.n, u.rows.node + a, c * 4);
+      memcpy(v.cnt + v.n, u.rows.cnt + a, c * 8);
+      v.n += c;
+    }
+    offs[t] = v.n;
+    if (t != nk[i]) return DG_E_INVAL; /* (a key list that was not ascending and unique) */
+    taken[who[i]].rows = v;
+    taken[who[i]].offs = offs;
   }
   return DG_OK;
 }

@@ -116,4 +116,38 @@ static inline uint64_t* rp_cont_room_keys(uint64_t* base, uint64_t off, rp_cont_
   return base + off + 2 * r.C + r.CB;
 }
 
+/* The row room of a hop that is answered with its rows (dg_merkle_continues_take), in page-locked
+ * words: R rows as rp_rows lays them out (columns at stride even(R)), then kcap + 1 offsets.
+ * dgr_take's "four rows per key" rule with a ceiling: R = min(rows_n, 4 * min(kcap, 4096) + 64),
+ * about 31 KB per hop at max_sync_size 200.  A hop that needs more takes its rows through
+ * dg_take_keysets afterwards. */
+typedef struct rp_take_room {
+  uint64_t R, kcap;
+} rp_take_room;
+static inline rp_take_room rp_take_room_for(uint64_t kcap, uint64_t rows_n) {
+  rp_take_room r;
+  r.R = rp_u64min(rows_n, 4 * rp_u64min(kcap, 4096) + 64);
+  r.kcap = kcap;
+  return r;
+}
+static inline uint64_t rp_take_room_words(rp_take_room r) { return rows_words(r.R) + even(r.kcap + 1); }
+/* The k hops' row rooms carved from ONE block (another than rp_cont_carve's), end to end: hop j's
+ * words are its rows [off[j], + rows_words(R)) | offsets [+ rows_words(R), + kcap + 1), each hop on
+ * a 16-byte boundary and no word shared.  Returns the block's words (off[k] is written too). */
+static inline uint64_t rp_take_carve(int k, const rp_take_room* room, uint64_t* off) {
+  uint64_t w = 0;
+  for (int j = 0; j < k; j++) {
+    off[j] = w;
+    w += rp_take_room_words(room[j]);
+  }
+  off[k] = w;
+  return w;
+}
+static inline dg_store rp_take_room_rows(uint64_t* base, uint64_t off, rp_take_room r) {
+  return rp_rows(base + off, even(r.R), 0, r.R);
+}
+static inline uint64_t* rp_take_room_offs(uint64_t* base, uint64_t off, rp_take_room r) {
+  return base + off + rows_words(r.R);
+}
+
 #endif /* DG_REPLICA_PACK_H */

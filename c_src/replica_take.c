@@ -77,6 +77,10 @@ static int take_home(dgr_state* s, int k, uint64_t m, uint64_t* nu, dg_store* ou
 int dgr_take(dgr_state* s, uint64_t version, const uint64_t* keys, uint64_t n_keys, dg_store* out) {
   if (!s || !out || (n_keys && !keys)) return DG_E_INVAL;
   TRY(check_version(s, version));
+  return ri_take(s, keys, n_keys, out);
+}
+
+int ri_take(dgr_state* s, const uint64_t* keys, uint64_t n_keys, dg_store* out) {
   dgr_engine* g = s->g;
   TRY(ri_grow_msg(g, n_keys + 1));
   const uint64_t nk = rp_sort_unique(keys, n_keys, g->h_msg);
@@ -98,6 +102,10 @@ int dgr_take_batch(dgr_state* s, uint64_t version, int k, const uint64_t* const*
   for (int i = 0; i < k; i++)
     if (n_keys[i] && !keys[i]) return DG_E_INVAL;
   TRY(check_version(s, version));
+  return ri_take_batch(s, k, keys, n_keys, out);
+}
+
+int ri_take_batch(dgr_state* s, int k, const uint64_t* const* keys, const uint64_t* n_keys, dgr_taken* out) {
   dgr_engine* g = s->g;
   /* ONE message and one copy: the k keysets, each sorted and unique */
   TRY(ri_grow_batch(g, (uint64_t)k));

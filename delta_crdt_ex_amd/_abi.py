@@ -148,6 +148,16 @@ class dg_cont_hop(C.Structure):
     ]
 
 
+class dg_cont_take(C.Structure):
+    """The rows of one hop of dg_merkle_continues_take: columns, cap and offs from the caller;
+    rows.n and rc written."""
+    _fields_ = [
+        ("rows", dg_store),
+        ("offs", VP),
+        ("rc", C.c_int),
+    ]
+
+
 DG_DIFF_OLD = 1
 DG_DIFF_NEW = 2
 
@@ -294,6 +304,9 @@ _SIGS = {
                                           C.POINTER(C.c_int)]),
     "dg_merkle_continues": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store), C.c_int,
                                       C.POINTER(dg_cont_hop), C.c_uint32, C.c_uint64]),
+    "dg_merkle_continues_take": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store), C.c_int,
+                                           C.POINTER(dg_cont_hop), C.POINTER(C.POINTER(dg_cont_take)),
+                                           C.c_uint32, C.c_uint64]),
     "dg_merkle_truncate": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_merkle_cont),
                                      C.c_uint64]),
     "dg_merkle_fold_roots": (C.c_int, [P64, C.c_uint32, P64]),

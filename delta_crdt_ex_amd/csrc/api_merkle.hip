@@ -282,16 +282,33 @@ int dg_merkle_continue_home(dg_engine* e, const dg_merkle* t, const dg_store* s,
 }
 
 static_assert(DG_CONT_BATCH_MAX == CONT_BATCH_MAX, "deltagpu.h's batch limit is the kernel's");
-static_assert(sizeof(ContHop) % sizeof(u64) == 0, "descriptors are whole words of the page-locked block");
+static_assert(sizeof(ContHop) % sizeof(u64) == 0 && sizeof(ContTakeHop) % sizeof(u64) == 0,
+              "descriptors are whole words of the page-locked block");
 
-int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
-                        uint32_t levels, uint64_t max) {
+}  // extern "C"
+
+namespace {
+
+// dg_merkle_continues (takes == nullptr) and dg_merkle_continues_take
+int merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
+                     dg_cont_take* const* takes, uint32_t levels, uint64_t max, const char* what) {
   if (!e) return fail(DG_E_INVAL, "null engine");
-  TRY(check_merkle(t, "dg_merkle_continues"));
-  TRY(check_store(s, "dg_merkle_continues"));
-  if (k < 0 || k > CONT_BATCH_MAX) return fail(DG_E_INVAL, "dg_merkle_continues: k = %d hops (0 .. %d)", k, CONT_BATCH_MAX);
-  if ((k > 0 && !hops) || levels < 1) return fail(DG_E_INVAL, "dg_merkle_continues: bad arguments");
+  TRY(check_merkle(t, what));
+  TRY(check_store(s, what));
+  if (k < 0 || k > CONT_BATCH_MAX) return fail(DG_E_INVAL, "%s: k = %d hops (0 .. %d)", what, k, CONT_BATCH_MAX);
+  if ((k > 0 && !hops) || levels < 1) return fail(DG_E_INVAL, "%s: bad arguments", what);
   if (k == 0) return DG_OK;
+  for (int j = 0; takes && j < k; j++) {
+    dg_cont_take* tk = takes[j];
+    if (!tk) continue;
+    if (!tk->offs) return fail(DG_E_INVAL, "%s: take %d: null offs", what, j);
+    const dg_store& r = tk->rows;
+    if (r.cap && (!r.key || !r.val || !r.ts || !r.node || !r.cnt))
+      return fail(DG_E_INVAL, "%s: take %d: null column with cap=%llu", what, j, (unsigned long long)r.cap);
+    if (!hops[j].keys || !hops[j].cap) return fail(DG_E_INVAL, "%s: take %d: its hop has no room for keys", what, j);
+    tk->rows.n = 0;
+    tk->rc = DG_OK;
+  }
   // each hop's own checks, exactly dg_merkle_continue_home's
   const u32 depth = t->depth;
   std::vector<std::string> msgs(k);
@@ -324,10 +341,14 @@ int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int
   if (nw) {
     TRY(set_device(e));
     TRY(settle(e));
-    const size_t desc_words = sizeof(ContHop) / sizeof(u64);
-    TRY(ensure_cont(e, (size_t)CONT_BATCH_MAX * (desc_words + CONT_HDR_STRIDE)));
+    // rows can only come of a leaf form: a batch without one that asks for rows is the plain launch
+    bool take = false;
+    for (u32 w = 0; takes && w < nw; w++) take |= takes[slot[w]] && hops[slot[w]].in->level == depth + 1;
+    const size_t desc_words = sizeof(ContHop) / sizeof(u64), take_words = sizeof(ContTakeHop) / sizeof(u64);
+    TRY(ensure_cont(e, (size_t)CONT_BATCH_MAX * (desc_words + CONT_HDR_STRIDE + (take ? take_words : 0))));
     ContHop* hd = e->h_cont.as<ContHop>();
     u64* hdr = e->h_cont.as<u64>() + (size_t)CONT_BATCH_MAX * desc_words;
+    ContTakeHop* td = (ContTakeHop*)(hdr + (size_t)CONT_BATCH_MAX * CONT_HDR_STRIDE);
     for (u32 w = 0; w < nw; w++) {
       const dg_cont_hop& h = hops[slot[w]];
       const dg_merkle_cont* in = h.in;
@@ -349,8 +370,17 @@ int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int
       d.keys = h.keys;
       d.kcap = h.cap;
       hd[w] = d;
+      if (take) {
+        ContTakeHop x{};
+        if (dg_cont_take* tk = leaf ? takes[slot[w]] : nullptr) {
+          x.rows = rows_out_of(&tk->rows);
+          x.rcap = tk->rows.cap;
+          x.offs = tk->offs;
+        }
+        td[w] = x;
+      }
     }
-    ContBatchArgs p{};
+    ContTakeArgs p{};
     p.t = merkle_of(t);
     p.s = rows_of(s);
     p.levels = levels;
@@ -361,7 +391,8 @@ int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int
     p.d_counts = e->d_counts;
     p.h_pub = e->d_pub;
     p.seq = ++e->pub_seq;
-    HIP_TRY(launch_cont_batch(p, nw, e->stream));
+    p.takes = td;
+    HIP_TRY(take ? launch_cont_take(p, nw, e->stream) : launch_cont_batch(p, nw, e->stream));
     TRY(wait_published(e, p.seq));
     for (u32 w = 0; w < nw; w++) {
       const int j = slot[w];
@@ -378,6 +409,11 @@ int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int
       } else if (r[0] == CS_OK) {
         h.n_keys = std::min<u64>(r[1], h.cap);
         h.n_total = r[1];
+        if (take && td[w].offs) {  // (written by the workgroup with every CS_OK of a leaf form)
+          dg_cont_take* tk = takes[j];
+          memcpy(&tk->rows.n, (const void*)(hdr + (size_t)w * CONT_HDR_STRIDE + CS_TAKEN), sizeof(u64));
+          if (tk->rows.n > tk->rows.cap) tk->rc = DG_E_CAPACITY;
+        }
       } else {
         h.out->level = (u32)r[3];
         h.out->n = r[1];
@@ -388,10 +424,25 @@ int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int
   }
   for (int j = 0; j < k; j++)
     if (hops[j].rc != DG_OK) {
-      fail(hops[j].rc, "dg_merkle_continues: hop %d: %s", j, msgs[j].c_str());
+      fail(hops[j].rc, "%s: hop %d: %s", what, j, msgs[j].c_str());
       break;
     }
   return DG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
+                        uint32_t levels, uint64_t max) {
+  return merkle_continues(e, t, s, k, hops, nullptr, levels, max, "dg_merkle_continues");
+}
+
+int dg_merkle_continues_take(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
+                             dg_cont_take* const* takes, uint32_t levels, uint64_t max) {
+  return merkle_continues(e, t, s, k, hops, takes, levels, max,
+                          takes ? "dg_merkle_continues_take" : "dg_merkle_continues");
 }
 
 int dg_merkle_truncate(dg_engine* e, const dg_merkle* t, dg_merkle_cont* cont, uint64_t max) {

@@ -590,6 +590,22 @@ struct ContBatchArgs {
   u64 seq;
 };
 hipError_t launch_cont_batch(const ContBatchArgs& p, u32 k, hipStream_t st);
+// dg_merkle_continues_take: the batch hop that also answers a leaf form's {:ok, keys} with the
+// kept keys' rows (cont_hop_kernel<true, true>).  takes[j] goes with hops[j], in the same
+// page-locked block; offs == nullptr: hop j wants no rows and is cont_hop_kernel<true>'s hop.
+// The row total goes to word CS_TAKEN of the hop's header slot, behind the CS_HDR words; it
+// is written only where the hop took rows (a leaf form in, rows asked for, a CS_OK header).
+constexpr int CS_TAKEN = 6;
+static_assert(CS_TAKEN >= CS_HDR && CS_TAKEN < CONT_HDR_STRIDE, "a free word of the header's slot");
+struct ContTakeHop {
+  RowsOut rows;  // the kept keys' rows, store order (host or device), rcap rows
+  u64 rcap;
+  u64* offs;     // kcap + 1: rows [offs[i], offs[i + 1]) are key i's
+};
+struct ContTakeArgs : ContBatchArgs {
+  const ContTakeHop* takes;
+};
+hipError_t launch_cont_take(const ContTakeArgs& p, u32 k, hipStream_t st);
 // prepare_partial_diff: level L's positions and node hashes (2^L entries)
 hipError_t launch_cont_prepare(const MerkleT& t, u32 L, u64* opos, u64* ohash, hipStream_t st);
 // partial diff.  scratch: 2 * ceil(n / 256) u64.

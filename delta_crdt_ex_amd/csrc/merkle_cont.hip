@@ -6,7 +6,8 @@
 // expanded `levels` levels down; at the bucket level the reply is a leaf-form continuation
 // (the sender's (key, leaf) pairs of the differing buckets), which the peer merges with its
 // own rows into keys.  cont_hop_kernel does one whole hop of a small continuation in one
-// workgroup (dg_merkle_continue_home), or k such hops in k workgroups (dg_merkle_continues).
+// workgroup (dg_merkle_continue_home), or k such hops in k workgroups (dg_merkle_continues), a
+// leaf form's kept keys then with their rows where asked for (dg_merkle_continues_take).
 #include <type_traits>
 
 #include "dg_home.h"
@@ -273,17 +274,33 @@ __device__ __forceinline__ u32 merge_regs(const BucketPairs& bp, const u64* pk, 
   return c;
 }
 
+// merge_bucket of the store's rows with the staged pairs.  INLINE: inlined at this call; the take
+// form is large enough that the compiler would otherwise call it, with the hop's arguments and the
+// tree passed through a stack frame (384 B of scratch)
+template <bool WRITE, bool INLINE>
+__device__ __forceinline__ u32 merge_big(const Rows& s, const TermH& th, u64 r, u64 re, const u64* pk, const u64* ph,
+                                         u64 j, u64 je, u64* out, u64 o, u64 cap) {
+  if constexpr (INLINE) {
+    [[clang::always_inline]] return merge_bucket<true, WRITE>(s, th, r, re, s, th, pk, ph, j, je, out, o, cap);
+  } else {
+    return merge_bucket<true, WRITE>(s, th, r, re, s, th, pk, ph, j, je, out, o, cap);
+  }
+}
+
 // dg_merkle_continues: the same hop by workgroup j of a grid of k <= CONT_BATCH_MAX, for hop j
 // of a batch (cont_hop_kernel<true>; <false> is the single hop above, instruction for
-// instruction).  The tree, the store, `levels` and `max` are the launch's; hop j's numbers
-// and pointers come from descriptor j (page-locked host memory, read through uniform loads),
-// its result header goes to slot j of hdr (page-locked too).  No workgroup waits for another.
+// instruction; <true, true> is the take form below, the same hop and completion).  The tree,
+// the store, `levels` and `max` are the launch's; hop j's numbers and pointers come from
+// descriptor j (page-locked host memory, read through uniform loads), its result header goes
+// to slot j of hdr (page-locked too).  No workgroup waits for another.
 //
 // Completion, and why the host that has seen `seq` sees every workgroup's writes:
 //   (1) every thread of a workgroup, after its last write to host memory (outputs, keys, the
-//       header), executes __threadfence_system(): a release fence at system scope -- the
-//       thread's earlier writes are performed with respect to the host before anything the
-//       thread, or a thread that synchronizes with it, does afterwards;
+//       header; in the take form also the rows, their offsets and the row total, all written
+//       by take_hop and its caller, before this point), executes __threadfence_system(): a
+//       release fence at system scope -- the thread's earlier writes are performed with respect
+//       to the host before anything the thread, or a thread that synchronizes with it, does
+//       afterwards;
 //   (2) the workgroup barrier orders all its threads' fences before lane 0's add to the
 //       arrival word (agent scope: the adds of one launch are a total order on one word);
 //   (3) the workgroup whose add returns gridDim.x - 1 has read, through the chain of
@@ -326,9 +343,151 @@ __device__ __forceinline__ ContSmallArgs hop_args(const ContBatchArgs& p) {
   return a;
 }
 
-template <bool BATCH>
+// ---- the batch hop with take (dg_merkle_continues_take): a leaf form's kept keys and their rows
+// The differing keys of one bucket in ascending order, each with its rows in the store:
+// emit(key, first row, rows), no rows for a key only the peer holds.  walk_regs is merge_regs
+// (a key's rows end at the next head bit), walk_global is merge_bucket over global memory.
+template <class F>
+__device__ __forceinline__ void walk_regs(const BucketPairs& bp, const u64* pk, const u64* ph, u64 j, u64 je,
+                                          F emit) {
+  const u32 m = (u32)(bp.re - bp.r);
+#pragma unroll
+  for (int i = 0; i < BR; i++) {
+    if (!(bp.head >> i & 1u)) continue;
+    const u64 k = bp.key[i];
+    const u32 rest = bp.head >> (i + 1);
+    const u32 n = (rest ? (u32)(i + 1) + (u32)__builtin_ctz(rest) : m) - (u32)i;
+    for (; j < je && pk[j] < k; j++) emit(pk[j], 0ull, 0ull);
+    if (j < je && pk[j] == k) {
+      if (ph[j] != bp.leaf[i]) emit(k, bp.r + i, (u64)n);
+      j++;
+    } else {
+      emit(k, bp.r + i, (u64)n);
+    }
+  }
+  for (; j < je; j++) emit(pk[j], 0ull, 0ull);
+}
+
+// the same keys again without the leaves: `taken` has bit i where walk_regs emitted the key
+// whose rows start at row i (a key only the peer holds is always emitted)
+template <class F>
+__device__ __forceinline__ void walk_taken(const BucketPairs& bp, u32 taken, const u64* pk, u64 j, u64 je, F emit) {
+  const u32 m = (u32)(bp.re - bp.r);
+#pragma unroll
+  for (int i = 0; i < BR; i++) {
+    if (!(bp.head >> i & 1u)) continue;
+    const u64 k = bp.key[i];
+    const u32 rest = bp.head >> (i + 1);
+    const u32 n = (rest ? (u32)(i + 1) + (u32)__builtin_ctz(rest) : m) - (u32)i;
+    for (; j < je && pk[j] < k; j++) emit(pk[j], 0ull, 0ull);
+    if (j < je && pk[j] == k) j++;
+    if (taken >> i & 1u) emit(k, bp.r + i, (u64)n);
+  }
+  for (; j < je; j++) emit(pk[j], 0ull, 0ull);
+}
+
+template <class F>
+__device__ __forceinline__ void walk_global(const Rows& s, const TermH& th, u64 ia, u64 ie, const u64* pk,
+                                            const u64* ph, u64 j, u64 je, F emit) {
+  while (ia < ie || j < je) {
+    const u64 ka = ia < ie ? s.key[ia] : ~0ull;
+    const u64 kb = j < je ? pk[j] : ~0ull;
+    const bool has_a = ia < ie && (j >= je || ka <= kb);
+    const bool has_b = j < je && (ia >= ie || kb <= ka);
+    const u64 k = has_a ? ka : kb;
+    const u64 a0 = ia;
+    u64 ha = 0, hb = 0;
+    if (has_a)
+      for (; ia < ie && s.key[ia] == k; ia++) ha += rh(s, ia, th);
+    if (has_b) hb = ph[j++];
+    if (!(has_a && has_b) || ha != hb) emit(k, a0, ia - a0);
+  }
+}
+
+// One leaf-form hop's keys and rows by its workgroup: this thread's bucket holds the keys
+// [ko, ko + c) of the hop's `tot`.  The keys below kcap are written as the plain hop writes
+// them and their rows counted in the same walk; a block scan gives this thread's row offset;
+// a second walk writes offs[] and, per CS_IN output rows, the rows' store indices into s_src
+// (s_dpos: unused by the leaf form), from which the whole workgroup copies the five columns with
+// consecutive lanes on consecutive rows -- whole lines to host memory, where a thread storing
+// its own keys' rows would store 8 bytes at a time.  More rows than rcap: only the total is
+// returned (nothing of rows or offs is written).  Every thread of the workgroup calls this.
+__device__ __forceinline__ u64 take_hop(const ContSmallArgs& a, const MerkleT& t, const ContTakeHop& tk,
+                                        const BucketPairs& bp, u64 j, u64 je, u32 c, u32 ko, u32 tot,
+                                        const u64* s_pk, const u64* s_ph, u64* s_src, u32* s_wave) {
+  const int tid = threadIdx.x;
+  const u64 kept = min<u64>(tot, a.kcap);
+  u64 rc = 0;  // the rows of this thread's kept keys
+  u32 taken = 0;
+  {
+    u32 x = 0;
+    auto emit = [&](u64 k, u64 r0, u64 n) __attribute__((always_inline)) {
+      const u64 pos = (u64)ko + x++;
+      if (pos < kept) {
+        a.keys[pos] = k;
+        rc += n;
+      }
+      if (n && !bp.big) taken |= 1u << (u32)(r0 - bp.r);
+    };
+    if (c) {
+      if (bp.big)
+        walk_global(a.s, t.th, bp.r, bp.re, s_pk, s_ph, j, je, emit);
+      else
+        walk_regs(bp, s_pk, s_ph, j, je, emit);
+    }
+  }
+  // a bucket counts its rows in 32 bits: the sum of 512 of them, each clamped to 2^22, is exact
+  // where it stays below 2^22; else the sums of the counts' 16-bit halves
+  constexpr u32 SMALL = 1u << 22;
+  u32 t32;
+  u64 ro = block_excl_scan<CSN>((u32)min<u64>(rc, SMALL), s_wave, &t32), rtot = t32;
+  if (t32 >= SMALL) {
+    u32 tl, th2;
+    const u32 el = block_excl_scan<CSN>((u32)(rc & 0xffffu), s_wave, &tl);
+    const u32 eh = block_excl_scan<CSN>((u32)(rc >> 16), s_wave, &th2);
+    ro = ((u64)eh << 16) + el;
+    rtot = ((u64)th2 << 16) + tl;
+  }
+  if (rtot > tk.rcap) return rtot;
+  if (tid == 0) tk.offs[kept] = rtot;
+  for (u64 base = 0; base == 0 || base < rtot; base += CS_IN) {
+    if (base) __syncthreads();  // the copy of the rows before
+    u32 x = 0;
+    u64 rq = ro;
+    auto emit = [&](u64, u64 r0, u64 n) __attribute__((always_inline)) {
+      const u64 pos = (u64)ko + x++;
+      if (pos >= kept) return;
+      if (base == 0) tk.offs[pos] = rq;
+      const u64 lo = max(rq, base), hi = min(rq + n, base + (u64)CS_IN);
+      for (u64 q = lo; q < hi; q++) s_src[q - base] = r0 + (q - rq);
+      rq += n;
+    };
+    if (c) {
+      if (bp.big)
+        walk_global(a.s, t.th, bp.r, bp.re, s_pk, s_ph, j, je, emit);
+      else
+        walk_taken(bp, taken, s_pk, j, je, emit);
+    }
+    __syncthreads();
+    const u64 m = min<u64>(rtot - base, (u64)CS_IN);
+    for (u64 q = tid; q < m; q += CSN) {
+      const u64 r = s_src[q];
+      tk.rows.key[base + q] = a.s.key[r];
+      tk.rows.val[base + q] = a.s.val[r];
+      tk.rows.ts[base + q] = a.s.ts[r];
+      tk.rows.node[base + q] = a.s.node[r];
+      tk.rows.cnt[base + q] = a.s.cnt[r];
+    }
+  }
+  return rtot;
+}
+
+template <bool BATCH, bool TAKE = false>
 __global__ __launch_bounds__(CSN) void cont_hop_kernel(
-    typename std::conditional<BATCH, ContBatchArgs, ContSmallArgs>::type p, MerkleT t) {
+    typename std::conditional<TAKE, ContTakeArgs,
+                              typename std::conditional<BATCH, ContBatchArgs, ContSmallArgs>::type>::type p,
+    MerkleT t) {
+  static_assert(BATCH || !TAKE, "the take form is a batch hop");
   __shared__ u64 s_dpos[CS_IN];
   __shared__ u64 s_pk[CS_IN], s_ph[CS_IN];  // leaf form in: the peer's pairs; node form: bucket rows
   __shared__ u32 s_wave[CSN / WAVE + 1];
@@ -479,7 +638,7 @@ __global__ __launch_bounds__(CSN) void cont_hop_kernel(
         bucket_pairs(t, a.s, b, bp);
         j = bucket_start(t, s_pk, a.n, b);
         je = bucket_start(t, s_pk, a.n, b + 1);
-        c = bp.big ? merge_bucket<true, false>(a.s, t.th, bp.r, bp.re, a.s, t.th, s_pk, s_ph, j, je, nullptr, 0, 0)
+        c = bp.big ? merge_big<false, TAKE>(a.s, t.th, bp.r, bp.re, s_pk, s_ph, j, je, nullptr, 0, 0)
                    : merge_regs<false>(bp, s_pk, s_ph, j, je, nullptr, 0, 0);
       }
     }
@@ -488,9 +647,18 @@ __global__ __launch_bounds__(CSN) void cont_hop_kernel(
     if (s_bad) {
       h[0] = CS_BAD;
     } else {
-      if (c) {
+      bool plain = true;
+      if constexpr (TAKE) {
+        const ContTakeHop& tk = p.takes[blockIdx.x];
+        if (tk.offs) {  // (uniform: the descriptor is the workgroup's)
+          plain = false;
+          const u64 rows = take_hop(a, t, tk, bp, j, je, c, ko, tot, s_pk, s_ph, s_dpos, s_wave);
+          if (tid == 0) a.home[CS_TAKEN] = rows;  // (a word of the slot past the CS_HDR written below)
+        }
+      }
+      if (plain && c) {
         if (bp.big)
-          merge_bucket<true, true>(a.s, t.th, bp.r, bp.re, a.s, t.th, s_pk, s_ph, j, je, a.keys, ko, a.kcap);
+          merge_big<true, TAKE>(a.s, t.th, bp.r, bp.re, s_pk, s_ph, j, je, a.keys, ko, a.kcap);
         else
           merge_regs<true>(bp, s_pk, s_ph, j, je, a.keys, ko, a.kcap);
       }
@@ -537,6 +705,11 @@ hipError_t launch_cont_small(const ContSmallArgs& a, hipStream_t st) {
 
 hipError_t launch_cont_batch(const ContBatchArgs& p, u32 k, hipStream_t st) {
   hipLaunchKernelGGL(cont_hop_kernel<true>, dim3(k), dim3(CSN), 0, st, p, p.t);
+  return hipGetLastError();
+}
+
+hipError_t launch_cont_take(const ContTakeArgs& p, u32 k, hipStream_t st) {
+  hipLaunchKernelGGL((cont_hop_kernel<true, true>), dim3(k), dim3(CSN), 0, st, p, p.t);
   return hipGetLastError();
 }
 

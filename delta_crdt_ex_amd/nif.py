@@ -25,6 +25,9 @@ shapes, so the Elixir dispatch of INTEGRATION.md §3 can be exercised without a 
                                                     -> ("continue", bytes) | ("ok", keys)
     merkle_continue_batch(state, version, [cont, ...], levels, max_sync_size | "infinite")
                                                     -> ("ok", [("continue", bytes) | ("ok", keys), ...])
+    merkle_continue_take_batch(state, version, [cont, ...], [want, ...], levels, max_sync_size | "infinite")
+                                                    -> ("ok", [("continue", bytes) | ("ok", keys)
+                                                               | ("ok", keys, value_map), ...])
     sweep(engine)                                   -> ("ok", {"values": (before, after),
                                                                "keys": (before, after)})
     resolve_keys(engine, keys)                      -> keys
@@ -73,6 +76,10 @@ class dgr_diffs(C.Structure):
 class dgr_changed(C.Structure):
     _fields_ = [("version", C.c_uint64), ("n_changed", C.c_uint64), ("keys", C.c_void_p),
                 ("rows", dg_store), ("ctx", dg_context)]
+
+
+class dgr_hop_rows(C.Structure):
+    _fields_ = [("rows", dg_store), ("offs", C.c_void_p)]
 
 
 class dgr_taken(C.Structure):
@@ -127,6 +134,8 @@ _SIGS = {
                                   C.POINTER(VP), PU64, C.POINTER(VP), PU64]),
     "dgr_merkle_continue_batch": (I32, [VP, U64, I32, C.POINTER(C.c_char_p), PU64, C.c_uint32, U64,
                                         C.POINTER(dgr_cont_result)]),
+    "dgr_merkle_continue_take_batch": (I32, [VP, U64, I32, C.POINTER(C.c_char_p), PU64, C.c_char_p, C.c_uint32,
+                                             U64, C.POINTER(dgr_cont_result), C.POINTER(dgr_hop_rows)]),
 }
 
 _lib = None
@@ -678,6 +687,43 @@ def merkle_continue_batch(state: State, version: int, conts, levels: int, max_sy
     return ("ok", out)
 
 
+def merkle_continue_take_batch(state: State, version: int, conts, want, levels: int, max_sync):
+    """merkle_continue_batch that also answers send_diff for the messages whose want[j] is set
+    (the originator of a sync: diff.originator != diff.to): element j is ("ok", keys, value_map)
+    where merkle_continue gives ("ok", keys) with keys, value_map what take(state, version, keys)[1]
+    is; every other element is merkle_continue_batch's.  One call per 64 messages
+    (dgr_merkle_continue_take_batch: the rows come out of the hops' own launch)."""
+    eng = state.engine
+    rc = eng.refresh_terms()
+    if rc:
+        return _err(rc)
+    mx = U64_MAX if max_sync == "infinite" else int(max_sync)
+    conts, want = list(conts), [1 if w else 0 for w in want]
+    if len(want) != len(conts):
+        return _err(_abi.DG_E_INVAL)
+    out = []
+    for c0 in range(0, len(conts), CONT_BATCH_MAX):
+        chunk = conts[c0:c0 + CONT_BATCH_MAX]
+        k = len(chunk)
+        bins = (C.c_char_p * k)(*chunk)
+        lens = (C.c_uint64 * k)(*[len(c) for c in chunk])
+        res = (dgr_cont_result * k)()
+        taken = (dgr_hop_rows * k)()
+        rc = eng.lib.dgr_merkle_continue_take_batch(state.ptr, version, k, bins, lens, bytes(want[c0:c0 + k]),
+                                                    levels, mx, res, taken)
+        if rc:
+            return _err(rc)
+        for r, t, w in zip(res, taken, want[c0:c0 + k]):
+            if r.rc:
+                out.append(_err(r.rc))
+            elif r.status == 1:
+                out.append(("continue", C.string_at(r.bin, r.len)))
+            else:
+                keys = [_key_term(eng, kid) for kid in _arr(r.keys, r.n_keys, np.uint64)]
+                out.append(("ok", keys, _unmarshal_rows(eng, t.rows)) if w and r.n_keys else ("ok", keys))
+    return ("ok", out)
+
+
 def sweep(engine: Engine, keys: bool = True):
     return engine.sweep(keys=keys)
 
@@ -707,5 +753,5 @@ def resolve_keys(engine: Engine, keys):
 __all__ = ["engine_open", "state_load", "join_delta", "mutate_batch", "join_delta_diffs",
            "mutate_batch_diffs", "join_deltas", "join_deltas_diffs", "classify_diffs", "read", "take",
            "take_batch",
-           "merkle_build", "merkle_prepare", "merkle_continue", "merkle_continue_batch", "sweep", "resolve_keys", "key_placeholder",
+           "merkle_build", "merkle_prepare", "merkle_continue", "merkle_continue_batch", "merkle_continue_take_batch", "sweep", "resolve_keys", "key_placeholder",
            "Engine", "State", "DGR_E_STALE"]

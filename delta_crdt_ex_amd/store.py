@@ -1136,6 +1136,93 @@ class Engine:
                 break
         return res
 
+    def merkle_continues_take(self, tree: MerkleTree, conts, want_rows, levels: int = 8,
+                              max_entries: int | None = None, caps=None, row_caps=None, retry: bool = True):
+        """dg_merkle_continues_take: merkle_continues whose {:ok, keys} hops with want_rows[j] set
+        also return Map.take(value, keys) of the keys they keep, out of the same launch and wait.
+        Such a hop keeps the first max_entries keys (truncate(keys, max_sync_size); None: all)
+        and its element is ("ok", keys, total, offs, Store): rows [offs[i], offs[i + 1]) of the
+        Store are keys[i]'s, what take_keys(tree.store, keys) returns.  Every other element is
+        merkle_continues'.  `row_caps`: per hop the rows its Store is first given (default:
+        take_keys'); a take that reports DG_E_CAPACITY is retried at the size it reported
+        (retry=False: ("ok", keys, total, None, ("capacity", rows needed)))."""
+        self._order()
+        conts = list(conts)
+        want = [bool(w) for w in want_rows]
+        k = len(conts)
+        assert len(want) == k
+        s = tree.store
+        mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
+        t, ss = tree.abi(), s.abi()
+        hops = (_abi.dg_cont_hop * max(k, 1))()
+        cins = [c.abi() for c in conts]
+        sizes, outs, cos, keys = [], [None] * k, [None] * k, []
+        rsize, rows, offs, takes = [0] * k, [None] * k, [None] * k, [None] * k
+        for j, c in enumerate(conts):
+            oc, ob = 4 * max(c.n, 1), max(c.n, 1)
+            if max_entries is not None:
+                oc = min(oc, max(int(max_entries), 1))
+            sizes.append(tuple(caps[j]) if caps is not None and caps[j] is not None else (oc, ob))
+            cap = max(c.n, 1) + s.n
+            if want[j] and max_entries is not None:
+                cap = min(cap, max(int(max_entries), 1))
+            keys.append(torch.empty(max(int(cap), 1), dtype=_I64, device=self.device))
+            hops[j].in_ = C.pointer(cins[j])
+            hops[j].keys = keys[j].data_ptr()
+            hops[j].cap = int(cap)
+            if want[j]:
+                # take_keys' rule: room for four rows per key, the store's rows at the most
+                rsize[j] = (int(row_caps[j]) if row_caps is not None and row_caps[j] is not None
+                            else min(max(s.n, 1), max(4 * int(cap), 256)))
+                offs[j] = torch.empty(int(cap) + 1, dtype=_I64, device=self.device)
+        todo = list(range(k))
+        res = [None] * k
+        for attempt in range(3):
+            batch = (_abi.dg_cont_hop * max(len(todo), 1))()
+            tptr = (C.POINTER(_abi.dg_cont_take) * max(len(todo), 1))()
+            for i, j in enumerate(todo):
+                outs[j] = MerkleCont.empty(sizes[j][0], sizes[j][1], self.device)
+                cos[j] = outs[j].abi()
+                hops[j].out = C.pointer(cos[j])
+                batch[i] = hops[j]
+                if want[j]:
+                    rows[j] = Store.empty(max(rsize[j], 1), self.device)
+                    takes[j] = _abi.dg_cont_take(rows=rows[j].abi(), offs=offs[j].data_ptr())
+                    takes[j].rows.cap = rsize[j]
+                    tptr[i] = C.pointer(takes[j])
+            check(self.lib.dg_merkle_continues_take(self.h, C.byref(t), C.byref(ss), len(todo), batch, tptr,
+                                                    levels, mx))
+            again = []
+            for i, j in enumerate(todo):
+                h = batch[i]
+                if h.rc == _abi.DG_E_CAPACITY and not retry:
+                    res[j] = ("capacity", int(cos[j].n), int(cos[j].n_buckets))
+                elif h.rc == _abi.DG_E_CAPACITY and attempt < 2:
+                    sizes[j] = (max(int(cos[j].n), sizes[j][0]), max(int(cos[j].n_buckets), sizes[j][1]))
+                    again.append(j)
+                elif h.rc != _abi.DG_OK:
+                    res[j] = ("error", h.rc)
+                elif h.status == _abi.DG_CONT_DECLINED:
+                    res[j] = ("declined",)
+                elif h.status == 1:
+                    outs[j]._set(cos[j])
+                    res[j] = ("continue", outs[j])
+                elif not want[j] or h.n_keys == 0:  # ({:ok, []} took no rows)
+                    res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total))
+                elif takes[j].rc == _abi.DG_E_CAPACITY and retry and attempt < 2:
+                    rsize[j] = int(takes[j].rows.n)
+                    again.append(j)
+                elif takes[j].rc == _abi.DG_E_CAPACITY:
+                    res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total), None, ("capacity", int(takes[j].rows.n)))
+                else:
+                    check(takes[j].rc)
+                    rows[j].n = int(takes[j].rows.n)
+                    res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total), offs[j][: h.n_keys + 1], rows[j])
+            todo = again
+            if not todo:
+                break
+        return res
+
     def merkle_truncate(self, tree: MerkleTree, cont: MerkleCont, max_entries: int) -> MerkleCont:
         """MerkleMap.truncate_diff(cont, max_sync_size) (causal_crdt.ex:98,212-214)."""
         c = cont.abi()

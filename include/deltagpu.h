@@ -687,6 +687,34 @@ typedef struct {
 int dg_merkle_continues(dg_engine* e, const dg_merkle* t, const dg_store* s, int k, dg_cont_hop* hops,
                         uint32_t levels, uint64_t max);
 
+/* dg_merkle_continues whose leaf-form hops also return Map.take(value, keys) of the keys they
+ * keep, in the same launch and the same wait: what the originator of a sync sends next
+ * (causal_crdt.ex:104-105, send_diff :324-335).  The workgroup that finds a differing key has
+ * that key's rows located already, so there is no key search and no second call.
+ * takes[j] == NULL: hop j wants no rows; takes == NULL: the call is dg_merkle_continues.
+ * Everything dg_merkle_continues says of `hops` holds unchanged.  For a hop with a take whose
+ * answer is {:ok, keys} (status == 0, rc == DG_OK):
+ *   rows            the rows of `s` whose key is among keys[0, n_keys), in store order,
+ *                   bit-identical to dg_take_keys(s, keys, n_keys); rows.n their number;
+ *   offs[0, n_keys] rows [offs[i], offs[i + 1]) are the rows of keys[i] (a key the store lacks:
+ *                   an empty range); offs[n_keys] == rows.n.
+ * More rows than rows.cap: the take's rc = DG_E_CAPACITY and rows.n = the rows needed (rows and
+ * offs then hold nothing); the hop's own rc, status, keys, n_keys and n_total are valid all the
+ * same.  For every other outcome of the hop (:continue, {:ok, []}, declined, an error) the take
+ * has rows.n = 0 and rc = DG_OK.  rows' columns and offs may be device memory or memory from
+ * dg_host_alloc.  Additional DG_E_INVAL cases of the call, found before any launch: a take with
+ * null offs, null columns with rows.cap > 0, a hop with a take but null keys or cap == 0.
+ * The takes' outputs (the columns, offs) MUST NOT overlap one another, any hop's output or any
+ * hop's input: the workgroups write them concurrently, and the call does not check. */
+typedef struct {
+  dg_store rows;  /* out: columns (device or dg_host_alloc memory), cap rows; n written by the call */
+  uint64_t* offs; /* the hop's keys cap + 1 entries */
+  int rc;         /* DG_OK, or DG_E_CAPACITY with rows.n = the rows needed */
+} dg_cont_take;
+int dg_merkle_continues_take(dg_engine* e, const dg_merkle* t, const dg_store* s, int k,
+                             dg_cont_hop* hops, dg_cont_take* const* takes,
+                             uint32_t levels, uint64_t max);
+
 /* MerkleMap.truncate_diff(cont, max) (causal_crdt.ex:98,212-214): keep the first `max`
  * entries of a node-form continuation, or the pairs of the first `max` buckets of a
  * leaf-form one (`t`: the tree that produced it; a leaf form needs one device
