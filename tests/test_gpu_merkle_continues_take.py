@@ -59,10 +59,10 @@ def assert_rows(engine, tree, rows_x, res, kept):
             assert np.array_equal(g, c)
 
 
-def check_take(engine, tree, rows_x, hops, max_sync, want, **kw):
+def check_take(engine, tree, rows_x, hops, max_sync, want, depth=8, **kw):
     """one batch through merkle_continues_take, every element against merkle_continues' and the
     oracle; returns the elements"""
-    conts = [dev_cont(rc, 8) for rc, _ in hops]
+    conts = [dev_cont(rc, depth) for rc, _ in hops]
     plain = engine.merkle_continues(tree, conts, 3, max_sync)
     got = engine.merkle_continues_take(tree, conts, want, 3, max_sync, **kw)
     assert len(got) == len(hops)
@@ -75,7 +75,7 @@ def check_take(engine, tree, rows_x, hops, max_sync, want, **kw):
         else:
             assert len(res) == len(pl)  # no rows: merkle_continues' element
             assert_same(res, pl)
-            assert_is(res, w, 8)
+            assert_is(res, w, depth)
     return got
 
 

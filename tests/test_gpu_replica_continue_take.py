@@ -11,6 +11,7 @@ import pytest
 
 import cont_batch_cases as B
 import partial_diff_cases as P
+import take_pass_cases as T
 from delta_crdt_ex_amd import _abi, nif
 from delta_crdt_ex_amd import workloads as W
 from test_gpu_replica_continue_batch import frame, load
@@ -124,6 +125,35 @@ def test_general_path_rows(eng):
     over = next(j for j, (rc, _) in enumerate(hops) if P.over_home_limits(rc))
     assert len(exp[over]) == 4 and len(exp[over][2][0]) > 512
     assert take_batch(x, x.version, msgs, want, 4, "infinite") == exp
+
+
+@pytest.mark.parametrize("max_sync", ["infinite", T.CUTS[0]])
+def test_multi_pass_rows_out_of_the_launch(eng, max_sync):
+    """take_pass_cases.stairs() at depth 9: keys hops of more than 4096 rows, which the launch
+    copies in several passes.  That the launch and not the fallback take serves them is the room
+    rule of replica_pack.h, restated: a hop has room for min(rows_n, 4 * min(kcap, 4096) + 64) rows,
+    kcap = min(max_sync, rows_n + n + 1, 65536).  Unbounded that is all 16,440 rows of X, which the
+    hop against the empty replica needs (five passes, the 8200-row key among them).  At the cut
+    the 8200-row key alone is over four rows a key, so it is kept out of the hop meant here: the
+    hop against the empty replica, cut before that key, needs 4760 rows of its 9052 (two passes),
+    while the hop against P, which holds the key, is over its room and comes through the
+    fallback beside it."""
+    ms = None if max_sync == "infinite" else max_sync
+    rows_x, _ = T.stairs()
+    hops = T.hops_of_conversations(ms)
+    keys_hops = [(rc, T.kept_of(w, ms)) for rc, w in hops if B.kind_of(w) == "keys"]
+    need = [T.row_total(rows_x, kept) for _, kept in keys_hops]
+    room = [min(len(rows_x[0]), 4 * min(min(len(rows_x[0]) + len(rc[2]) + 1, 65536, *([ms] if ms else [])), 4096) + 64)
+            for rc, _ in keys_hops]
+    assert room == [T.replica_room(len(rows_x[0]), len(rc[2]), ms) for rc, _ in keys_hops]
+    served = [n for n, r in zip(need, room) if n <= r]
+    assert max(served) > 4096 and (ms is not None or max(served) == max(need) == len(rows_x[0]))
+    x = load(eng, rows_x, T.DEPTH)
+    msgs = [frame(rc, T.DEPTH) for rc, _ in hops]
+    want = [True] * len(msgs)
+    exp = two_calls(x, x.version, msgs, want, T.LEVELS, max_sync)
+    assert sorted(len(e[2][0]) for e in exp if len(e) == 4) == sorted(need)
+    assert take_batch(x, x.version, msgs, want, T.LEVELS, max_sync) == exp
 
 
 def overflow_pair():
