@@ -72,6 +72,12 @@ int ri_grow_batch(dgr_engine* g, uint64_t k) {
 }
 
 /* ------------------------------------------------------------ engine */
+int dgr_deltas_route_stats(const dgr_engine* g, uint64_t out[3]) {
+  if (!g || !out) return DG_E_INVAL;
+  memcpy(out, g->keyed_stats, sizeof g->keyed_stats);
+  return DG_OK;
+}
+
 int dgr_engine_open(int device, dgr_engine** out) {
   if (!out) return DG_E_INVAL;
   *out = NULL;
@@ -84,6 +90,9 @@ int dgr_engine_open(int device, dgr_engine** out) {
   }
   g->th_stale = 1;
   g->mctx.kind = DG_CTX_DOTS;
+  const char* route = getenv("DGR_DELTAS_ROUTE"); /* (tests and A/B: force dgr_join_deltas' route) */
+  if (route && strcmp(route, "keyed") == 0) g->deltas_route = DGR_ROUTE_KEYED;
+  if (route && strcmp(route, "stream") == 0) g->deltas_route = DGR_ROUTE_STREAM;
   *out = g;
   return DG_OK;
 }

@@ -152,12 +152,23 @@ int dgr_mutate_batch_diffs(dgr_state* s, uint64_t version, uint32_t node, uint64
  * made per delta are not reproduced (a key whose read went a -> b -> a reports nothing).
  * Versions are dgr_join_delta's: one step for the batch, DGR_E_STALE for an older struct,
  * and any error after the device was touched moves the version on.  k == 1 is
- * dgr_join_delta[_diffs]; k == 0 changes nothing (no keys, the context, the same version). */
+ * dgr_join_delta[_diffs]; k == 0 changes nothing (no keys, the context, the same version).
+ * Under DGR_DELTAS_ROUTE=keyed (the environment at dgr_engine_open) the batch first tries
+ * dg_join_deltas_keyed (the fold per key of the keysets' union, no row outside it read) and
+ * takes dg_join_deltas when that declines: the same results either way.  =stream, =auto and
+ * no setting are the streaming call alone (auto waits for a table measured through this
+ * layer). */
 int dgr_join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
                     const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out);
 int dgr_join_deltas_diffs(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
                           const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out,
                           dgr_diffs* diffs);
+
+/* How often this engine's dgr_join_deltas[_diffs] tried dg_join_deltas_keyed, was served by it,
+ * and was declined (DG_KEYED_FALLBACK: the streaming call then ran): out[DGR_KEYED_TRIED],
+ * out[DGR_KEYED_SERVED], out[DGR_KEYED_DECLINED].  For tests and A/B of the routes. */
+enum { DGR_KEYED_TRIED = 0, DGR_KEYED_SERVED = 1, DGR_KEYED_DECLINED = 2 };
+int dgr_deltas_route_stats(const dgr_engine* g, uint64_t out[3]);
 
 /* The batch's packed message, host code only (dgr_join_deltas packs with these; the host test
  * c_src/test_batch.c checks them).  dgr_batch_words: its length in 8-byte words.

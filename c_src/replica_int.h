@@ -85,7 +85,13 @@ struct dgr_engine {
   /* dgr_sweep: the live states' stores as one host array */
   dg_store* sw_stores;
   uint64_t sw_cap;
+  /* dgr_join_deltas' route (DGR_DELTAS_ROUTE=stream|keyed|auto, read at engine open), and how
+   * often it tried dg_join_deltas_keyed, was served and was declined (dgr_deltas_route_stats) */
+  int deltas_route;
+  uint64_t keyed_stats[3];
 };
+
+enum { DGR_ROUTE_AUTO = 0, DGR_ROUTE_STREAM = 1, DGR_ROUTE_KEYED = 2 };
 
 #define TRY(x)                     \
   do {                             \

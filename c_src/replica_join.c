@@ -218,6 +218,13 @@ int dgr_join_delta_diffs(dgr_state* s, uint64_t version, const dg_store* delta, 
   return diffs ? join_delta(s, version, delta, delta_ctx, keys, n_keys, out, diffs) : DG_E_INVAL;
 }
 
+/* Which batches try dg_join_deltas_keyed first (g->deltas_route, DGR_DELTAS_ROUTE at engine
+ * open): `keyed` every batch, `stream` none.  `auto` is to be the region where the keyed call
+ * measures faster than both the streaming call and k single joins THROUGH THIS LAYER; that
+ * table does not exist yet (DESIGN 4.17 has figures of the library calls only), so auto is
+ * stream. */
+static int keyed_wanted(const dgr_engine* g) { return g->deltas_route == DGR_ROUTE_KEYED; }
+
 /* dgr_join_deltas (diffs NULL) and dgr_join_deltas_diffs */
 static int join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* deltas, const dg_context* ctxs,
                        const uint64_t* const* keys, const uint64_t* n_keys, dgr_changed* out, dgr_diffs* diffs) {
@@ -274,9 +281,22 @@ static int join_deltas(dgr_state* s, uint64_t version, int k, const dg_store* de
     TRY(ctx_home(s, &v.co));
     return bring_home(s, 0, &v, out, diffs);
   }
-  const int rc = dg_join_deltas(g->e, &s->rows, &s->ctx, k, g->b_rows, g->b_ctx, g->b_keys, g->b_nk, &s->spare,
-                                s->has_tree ? &s->tree : NULL, rp_back_keys(g->h_back), g->back_s, &n_changed,
-                                &v.tk, &v.co, diffs ? &v.dd : NULL);
+  /* small sync deltas: the fold at the cost of the keys they name (dg_join_deltas_keyed); a
+   * batch it declines has touched nothing and takes the streaming call */
+  int rc = DG_KEYED_FALLBACK;
+  if (keyed_wanted(g)) {
+    int swapped = 0;
+    rc = dg_join_deltas_keyed(g->e, &s->rows, &s->ctx, k, g->b_rows, g->b_ctx, g->b_keys, g->b_nk, &s->spare,
+                              s->has_tree ? &s->tree : NULL, rp_back_keys(g->h_back), g->back_s, &n_changed,
+                              &v.tk, &v.co, diffs ? &v.dd : NULL, &swapped);
+    g->keyed_stats[DGR_KEYED_TRIED]++;
+    if (rc == DG_KEYED_FALLBACK) g->keyed_stats[DGR_KEYED_DECLINED]++;
+    if (rc == DG_OK) g->keyed_stats[DGR_KEYED_SERVED]++;
+  }
+  if (rc == DG_KEYED_FALLBACK)
+    rc = dg_join_deltas(g->e, &s->rows, &s->ctx, k, g->b_rows, g->b_ctx, g->b_keys, g->b_nk, &s->spare,
+                        s->has_tree ? &s->tree : NULL, rp_back_keys(g->h_back), g->back_s, &n_changed, &v.tk,
+                        &v.co, diffs ? &v.dd : NULL);
   s->version++; /* applied, or failed: either way no older struct reads the device again */
   TRY(rc);
   return bring_home(s, n_changed, &v, out, diffs);

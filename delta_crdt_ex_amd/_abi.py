@@ -44,6 +44,7 @@ DG_E_CLAUSE = -6
 
 DG_HOME_FALLBACK = 1
 DG_CONT_DECLINED = 2
+DG_KEYED_FALLBACK = 3
 DG_CONT_HOME_ENTRIES = 4096
 DG_CONT_HOME_BUCKETS = 512
 DG_HOME_KEYS = 8
@@ -255,6 +256,11 @@ _SIGS = {
                                  C.POINTER(C.c_void_p), P64, C.POINTER(dg_store), C.c_void_p, P64,
                                  C.c_uint64, P64, C.POINTER(dg_store), C.POINTER(dg_context),
                                  C.POINTER(dg_lww_diffs)]),
+    "dg_join_deltas_keyed": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context), C.c_int,
+                                       C.POINTER(dg_store), C.POINTER(dg_context),
+                                       C.POINTER(C.c_void_p), P64, C.POINTER(dg_store), C.c_void_p, P64,
+                                       C.c_uint64, P64, C.POINTER(dg_store), C.POINTER(dg_context),
+                                       C.POINTER(dg_lww_diffs), C.POINTER(C.c_int)]),
     "dg_context_union": (C.c_int, [C.c_void_p, C.POINTER(dg_context), C.POINTER(dg_context),
                                    C.POINTER(dg_context)]),
     "dg_compress_dots": (C.c_int, [C.c_void_p, C.POINTER(dg_context), C.POINTER(dg_context)]),

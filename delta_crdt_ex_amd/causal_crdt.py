@@ -122,8 +122,9 @@ def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys,
 
 def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tree=None):
     """update_resident_state_with_delta for a batch [(delta, keys), ...] -- the pending
-    {:diff, delta, keys} messages of a replica's mailbox -- as ONE call (Engine.join_deltas:
-    the fold, the changed keys, the MerkleMap step and both reads).  `state` becomes the fold
+    {:diff, delta, keys} messages of a replica's mailbox -- as ONE call (Engine.join_deltas_keyed, or
+    Engine.join_deltas for a batch that declines: the fold, the changed keys, the MerkleMap
+    step and both reads; the keyed attempt is made whatever the state's size, see below).  `state` becomes the fold
     of the joins through `spare`, and the same `diffs` value is returned, NET over the batch:
     a key is reported once, with its read before the first and after the last delta (a key
     whose read went a -> b -> a reports nothing; the per-delta callbacks the reference would
@@ -157,8 +158,14 @@ def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tr
         for f in ("key", "val", "ts", "node", "cnt"):
             setattr(spare, f, getattr(grown, f))
     state._host = None
-    changed, old_val, new_val, flags, _ = eng.join_deltas(rows, ctx, [d.rows for d, _ in batch],
-                                                          [d.ctx for d, _ in batch], kts, spare, tree)
+    args = (rows, ctx, [d.rows for d, _ in batch], [d.ctx for d, _ in batch], kts, spare, tree)
+    # the fold per key of the keysets' union where the library serves the batch (VV contexts,
+    # every delta row's key in its keyset), else the streaming fold: the same results.  This
+    # mirror always tries the keyed call: on a state of about a million keys that is slower
+    # than the streaming fold alone at every batch size measured, and a batch
+    # declined on the device has paid for the attempt before the streaming fold runs.
+    got = eng.join_deltas_keyed(*args)
+    changed, old_val, new_val, flags, _ = got if got is not None else eng.join_deltas(*args)
     if changed.numel() == 0:
         return None
     return _callback_diffs(U, order, u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())

@@ -47,6 +47,143 @@ int tree_update(dg_engine* e, dg_merkle* t, const dg_store* olds, const dg_store
   return DG_OK;
 }
 
+// ---- the one-wait chain's host half, shared by dg_join_delta (kd_count_kernel) and
+//      dg_join_deltas_keyed (kk_count_kernel): everything of KdArgs but the delta side
+//      (d, cd, cu_tmp), and what follows the count launch.
+int kd_fill_args(dg_engine* e, KdArgs* pp, TreeScratch* ts, dg_store* state, dg_context* state_ctx,
+                 const uint64_t* keys, u64 nk, const KdScratch& k, dg_store* spare, dg_merkle* tree, uint64_t* changed,
+                 uint64_t cap, dg_store* rows, dg_context* ctx_out, const dg_lww_diffs* diffs) {
+  KdArgs& p = *pp;
+  p.a = rows_of(state);
+  p.aw = rows_out_of(state);
+  p.ca = ctx_of(state_ctx);
+  p.ca_node = state_ctx->node;
+  p.ca_cnt = state_ctx->cnt;
+  p.ca_cap = state_ctx->cap;
+  p.keys = keys;
+  p.nk = nk;
+  p.a_lo = k.a_lo;
+  p.d_lo = k.d_lo;
+  p.runs = k.runs;
+  p.amask = k.amask;
+  p.dmask = k.dmask;
+  p.dh = k.dh;
+  p.end = k.end;
+  p.shift = k.shift;
+  p.part = k.part;
+  p.tile_u0 = k.tile_u0;
+  p.uc_cnt = k.uctx.cnt;
+  p.uc_node = k.uctx.node;
+  if (diffs) {  // the per-key winners
+    p.has_diffs = 1;
+    p.dv_old = k.dv_old;
+    p.dv_new = k.dv_new;
+    p.old_val = diffs->old_val;
+    p.new_val = diffs->new_val;
+    p.dflags = diffs->flags;
+  }
+  p.ntiles = (nk + KD_BLOCK - 1) / KD_BLOCK;
+  p.changed = changed;
+  p.cap = cap;
+  p.has_rows = rows != nullptr;
+  if (rows) {
+    p.rows = rows_out_of(rows);
+    p.rows_cap = rows->cap;
+  }
+  p.sp = rows_out_of(spare);
+  if (ctx_out) {
+    p.co_node = ctx_out->node;
+    p.co_cnt = ctx_out->cnt;
+    p.co_cap = ctx_out->cap;
+  }
+  p.a_tiles = splice_tiles(state->n);
+  p.has_tree = tree != nullptr;
+  if (tree) p.t = merkle_of(tree);
+  p.d_counts = e->d_counts;
+  p.arrive = e->ticket + KD_ARRIVE;
+  p.err = e->ticket + KD_ERR;
+  // the tree update's scratch: hand-off words (engine scratch), and the dirty flags and
+  // chunk row-count changes in a buffer of their own that stays zero between calls
+  *ts = TreeScratch{};
+  if (tree) {
+    const u64 cw = merkle_ctr_words(tree->depth), chunks = merkle_chunks(tree->depth);
+    Arena mh, mz;
+    tree_layout(mh, mz, cw, chunks);
+    TRY(ensure_tmp(e, mh.bytes()));
+    TRY(ensure_kdz(e, mz.bytes()));
+    Arena hand(e->tmp.p), flags(e->kdz.p);
+    *ts = tree_layout(hand, flags, cw, chunks);
+  }
+  p.dirty = ts->dirty;
+  p.cdelta = ts->cdelta;
+  return DG_OK;
+}
+
+// Behind the count launch: the write beside the tree's re-reduction, the moved rows' copy, the
+// ONE publish and wait, then the outcome.  *declined = the guard's KD_BAD | KD_BIG bits (the
+// count kernel does not serve the input: nothing was written and the tree's put/delete has been
+// undone; DG_OK); more changed keys than `cap` and a tree input error are returned, all or nothing.
+int kd_finish_join(dg_engine* e, const KdArgs& p, const TreeScratch& ts, dg_store* state, dg_context* state_ctx,
+                   dg_store* spare, dg_merkle* tree, uint64_t* n_changed, int* swapped, dg_store* rows,
+                   dg_context* ctx_out, const char* what, u64* declined) {
+  *declined = 0;
+  u32* err = p.err;
+  HIP_TRY(launch_kd_finish(p, ts.dirty, e->ticket + MERKLE_ARRIVE, ts.hand, ts.cdelta, e->stream));
+  SpliceArgs sp{};
+  sp.a = rows_of(state);
+  sp.keys = p.keys;
+  sp.nk = p.nk;
+  sp.a_lo = p.a_lo;
+  sp.end = p.end;
+  sp.shift = p.shift;
+  sp.tile_u0 = p.tile_u0;
+  sp.out = rows_out_of(spare);
+  sp.run_if = e->d_counts + KC_MOVED;
+  sp.kguard = e->d_counts + KC_GUARD;
+  sp.h_pub = e->d_pub;
+  sp.pub_counts = e->d_counts;
+  sp.seq = ++e->pub_seq;
+  sp.arrive_all = e->ticket + SPL_ARRIVE;
+  HIP_TRY(launch_splice_move(sp, e->stream));
+  TRY(wait_published(e, sp.seq));
+  TRY(published_errors(e));
+  const u64 g = e->h_counts[KC_GUARD];
+  const u32 tbits = e->h_ticket[KD_ERR];
+  if (g || (tbits & MERKLE_INPUT_ERR)) {
+    // nothing of the state or its context was written (the write kernel saw the guard or
+    // the error word), but the count kernel put the changes into the tree: the same update
+    // with the opposite sign restores every bucket node and count bit for bit.
+    *declined = g & (KD_BAD | KD_BIG);
+    const int rc = *declined ? DG_OK
+                   : (g & KD_CAP) ? fail(DG_E_CAPACITY, "%s: %llu changed keys > cap %llu", what,
+                                         (unsigned long long)e->h_counts[KC_CHANGED], (unsigned long long)p.cap)
+                                  : tree_input_error(tbits, what);
+    if (!tree) return rc;
+    // (dirty and cdelta are zero again: the re-reduction consumed them)
+    return undo_tree_update(e, rc, err, [&]() -> int {
+      HIP_TRY(launch_kd_tree(merkle_of(tree), p.keys, p.runs, p.dh, p.nk, nullptr, -1, ts.dirty,
+                             e->ticket + MERKLE_ARRIVE, ts.hand, ts.cdelta, err, e->stream));
+      return DG_OK;
+    });
+  }
+  if (e->h_counts[KC_MOVED]) {  // the state is in `spare`
+    const u64 n = state->n - e->h_counts[KC_TAKEN] + e->h_counts[KC_EDIT];
+    std::swap(*state, *spare);
+    state->n = n;
+    *swapped = 1;
+  }
+  state_ctx->n = e->h_counts[KC_CTX];
+  state_ctx->kind = DG_CTX_VV;
+  if (tree) tree->n_keys += e->h_counts[KC_DKEYS];
+  *n_changed = e->h_counts[KC_CHANGED];
+  if (rows) rows->n = e->h_counts[KC_ROWS];  // (more than rows->cap: not written, as the caller's contract says)
+  if (ctx_out) {
+    ctx_out->n = state_ctx->n;  // (more than ctx_out->cap: not written)
+    ctx_out->kind = DG_CTX_VV;
+  }
+  return DG_OK;
+}
+
 extern "C" {
 
 // dg_join_delta_rows' output: the changed keys' rows of `src`; more than rows->cap is
@@ -92,133 +229,19 @@ static int kd_join_delta(dg_engine* e, dg_store* state, dg_context* state_ctx, c
                      diffs != nullptr);
   }, &k));
   KdArgs p{};
-  p.a = rows_of(state);
-  p.aw = rows_out_of(state);
-  p.ca = ctx_of(state_ctx);
-  p.ca_node = state_ctx->node;
-  p.ca_cnt = state_ctx->cnt;
-  p.ca_cap = state_ctx->cap;
+  TreeScratch ts{};
+  TRY(kd_fill_args(e, &p, &ts, state, state_ctx, keys, nk, k, spare, tree, changed, cap, rows, ctx_out, diffs));
   p.d = rows_of(delta);
   p.cd = ctx_of(delta_ctx);
-  p.keys = keys;
-  p.nk = nk;
-  p.a_lo = k.a_lo;
-  p.d_lo = k.d_lo;
-  p.runs = k.runs;
-  p.amask = k.amask;
-  p.dmask = k.dmask;
-  p.dh = k.dh;
-  p.end = k.end;
-  p.shift = k.shift;
-  p.part = k.part;
-  p.tile_u0 = k.tile_u0;
-  p.uc_cnt = k.uctx.cnt;
-  p.uc_node = k.uctx.node;
   p.cu_tmp = k.cu_tmp;
-  if (diffs) {  // dg_join_delta_diffs: the per-key winners
-    p.has_diffs = 1;
-    p.dv_old = k.dv_old;
-    p.dv_new = k.dv_new;
-    p.old_val = diffs->old_val;
-    p.new_val = diffs->new_val;
-    p.dflags = diffs->flags;
-  }
-  p.ntiles = ntiles;
-  p.changed = changed;
-  p.cap = cap;
-  p.has_rows = rows != nullptr;
-  if (rows) {
-    p.rows = rows_out_of(rows);
-    p.rows_cap = rows->cap;
-  }
-  p.sp = rows_out_of(spare);
-  if (ctx_out) {
-    p.co_node = ctx_out->node;
-    p.co_cnt = ctx_out->cnt;
-    p.co_cap = ctx_out->cap;
-  }
-  p.a_tiles = a_tiles;
-  p.has_tree = tree != nullptr;
-  if (tree) p.t = merkle_of(tree);
-  p.d_counts = e->d_counts;
-  p.arrive = e->ticket + KD_ARRIVE;
-  // the tree update's scratch: hand-off words (engine scratch), and the dirty flags and
-  // chunk row-count changes in a buffer of their own that stays zero between calls
-  TreeScratch ts{};
-  u32* err = e->ticket + KD_ERR;
-  p.err = err;
-  if (tree) {
-    const u64 cw = merkle_ctr_words(tree->depth), chunks = merkle_chunks(tree->depth);
-    Arena mh, mz;
-    tree_layout(mh, mz, cw, chunks);
-    TRY(ensure_tmp(e, mh.bytes()));
-    TRY(ensure_kdz(e, mz.bytes()));
-    Arena hand(e->tmp.p), flags(e->kdz.p);
-    ts = tree_layout(hand, flags, cw, chunks);
-  }
-  p.dirty = ts.dirty;
-  p.cdelta = ts.cdelta;
   // three launches, one wait: the count (the per-key joins, the tree's put/delete, the scan
   // and the context union by its last workgroup), the write beside the tree's re-reduction,
   // the moved rows' copy (its last workgroup publishes the count block)
   HIP_TRY(launch_kd_join(p, e->stream));
-  HIP_TRY(launch_kd_finish(p, ts.dirty, e->ticket + MERKLE_ARRIVE, ts.hand, ts.cdelta, e->stream));
-  SpliceArgs sp{};
-  sp.a = rows_of(state);
-  sp.keys = keys;
-  sp.nk = nk;
-  sp.a_lo = p.a_lo;
-  sp.end = p.end;
-  sp.shift = p.shift;
-  sp.tile_u0 = p.tile_u0;
-  sp.out = rows_out_of(spare);
-  sp.run_if = e->d_counts + KC_MOVED;
-  sp.kguard = e->d_counts + KC_GUARD;
-  sp.h_pub = e->d_pub;
-  sp.pub_counts = e->d_counts;
-  sp.seq = ++e->pub_seq;
-  sp.arrive_all = e->ticket + SPL_ARRIVE;
-  HIP_TRY(launch_splice_move(sp, e->stream));
-  TRY(wait_published(e, sp.seq));
-  TRY(published_errors(e));
-  const u64 g = e->h_counts[KC_GUARD];
-  const u32 tbits = e->h_ticket[KD_ERR];
-  if (g || (tbits & MERKLE_INPUT_ERR)) {
-    // nothing of the state or its context was written (the write kernel saw the guard or
-    // the error word), but the count kernel put the changes into the tree: the same update
-    // with the opposite sign restores every bucket node and count bit for bit.
-    // (DG_OK with *done false: a delta row outside the keyset or a long key run -- the full
-    // join or the splice applies)
-    const int rc = (g & (KD_BAD | KD_BIG)) ? DG_OK
-                   : (g & KD_CAP) ? fail(DG_E_CAPACITY, "dg_join_delta: %llu changed keys > cap %llu",
-                                         (unsigned long long)e->h_counts[KC_CHANGED], (unsigned long long)cap)
-                                  : tree_input_error(tbits, "dg_join_delta");
-    if (!tree) return rc;
-    // (dirty and cdelta are zero again: the re-reduction consumed them)
-    return undo_tree_update(e, rc, err, [&]() -> int {
-      HIP_TRY(launch_kd_tree(merkle_of(tree), keys, p.runs, p.dh, nk, nullptr, -1, ts.dirty,
-                             e->ticket + MERKLE_ARRIVE, ts.hand, ts.cdelta, err, e->stream));
-      return DG_OK;
-    });
-  }
-  const u64 n_e = e->h_counts[KC_EDIT], n_chg = e->h_counts[KC_CHANGED], n_rows = e->h_counts[KC_ROWS];
-  const u64 n_ak = e->h_counts[KC_TAKEN], dk = e->h_counts[KC_DKEYS];
-  if (e->h_counts[KC_MOVED]) {  // the state is in `spare`
-    const u64 n = state->n - n_ak + n_e;
-    std::swap(*state, *spare);
-    state->n = n;
-    *swapped = 1;
-  }
-  state_ctx->n = e->h_counts[KC_CTX];
-  state_ctx->kind = DG_CTX_VV;
-  if (tree) tree->n_keys += dk;
-  *n_changed = n_chg;
-  if (rows) rows->n = n_rows;  // (more than rows->cap: not written, as the caller's contract says)
-  if (ctx_out) {
-    ctx_out->n = state_ctx->n;  // (more than ctx_out->cap: not written)
-    ctx_out->kind = DG_CTX_VV;
-  }
-  *done = true;
+  u64 declined = 0;
+  TRY(kd_finish_join(e, p, ts, state, state_ctx, spare, tree, n_changed, swapped, rows, ctx_out, "dg_join_delta",
+                     &declined));
+  *done = declined == 0;
   return DG_OK;
 }
 

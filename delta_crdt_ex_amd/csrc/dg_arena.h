@@ -380,4 +380,48 @@ inline TakesetsScratch takesets_layout(Arena& a, uint64_t k, size_t seg_bytes, u
   return s;
 }
 
+// dg_join_deltas_keyed (engine kdb).  The union's part is dg_take_keysets': the keyset
+// descriptors (k + 1) and the run descriptors (k), both staged in pinned memory first | the m
+// items end to end and their set numbers | the union in sorted order | the sort's scratch.
+// Behind it what outlives the union: the union keys and masks (m) | the two VV tables
+// (k * nodes each), the flag and the edit store's bump pointer -- zero_bytes from tabC on,
+// zeroed per call | the edit store (e_rows) | the one-wait path's own layout for m keys
+// (kd_layout: the union has at most m keys).
+struct KeyedScratch {
+  void *segs, *runs;
+  uint64_t* cat;
+  uint8_t* set;
+  uint64_t* usorted;
+  void* sort_tmp;
+  uint64_t *ukeys, *masks;
+  uint64_t *tabC, *tabP;
+  uint32_t* flag;
+  uint64_t* e_next;
+  size_t zero_bytes;
+  dg_store ed;
+  KdScratch kd;
+};
+inline KeyedScratch keyed_layout(Arena& a, uint64_t k, size_t seg_bytes, size_t run_bytes, uint64_t m,
+                                 size_t sort_bytes, uint64_t nodes, uint64_t e_rows, uint64_t part_words,
+                                 uint64_t a_tiles, uint64_t uctx_cap, bool diffs) {
+  KeyedScratch s;
+  s.segs = a.take<char>((k + 1) * seg_bytes);
+  s.runs = a.take<char>(k * run_bytes);
+  s.cat = a.take<uint64_t>(m);
+  s.set = a.take<uint8_t>(m);
+  s.usorted = a.take<uint64_t>(m);
+  s.sort_tmp = a.take<char>(sort_bytes);
+  s.ukeys = a.take<uint64_t>(m);
+  s.masks = a.take<uint64_t>(m);
+  const size_t z0 = a.off;
+  s.tabC = a.take<uint64_t>(k * nodes);
+  s.tabP = a.take<uint64_t>(k * nodes);
+  s.flag = a.take<uint32_t>(1);
+  s.e_next = a.take<uint64_t>(1);
+  s.zero_bytes = a.off - z0;
+  s.ed = a.store(e_rows);
+  s.kd = kd_layout(a, m, part_words, a_tiles, uctx_cap, 0, diffs);
+  return s;
+}
+
 }  // namespace dg

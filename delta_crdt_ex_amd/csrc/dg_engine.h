@@ -232,6 +232,14 @@ int splice_edit(dg_engine* e, Splice* w, const dg_context* ca, const dg_store* b
 int tree_update(dg_engine* e, dg_merkle* t, const dg_store* olds, const dg_store* news, const uint64_t* keys,
                 uint64_t n_keys, const char* what);
 
+// the one-wait chain's host half around a count launch (dg_join_delta, dg_join_deltas_keyed)
+int kd_fill_args(dg_engine* e, KdArgs* p, TreeScratch* ts, dg_store* state, dg_context* state_ctx,
+                 const uint64_t* keys, u64 nk, const KdScratch& k, dg_store* spare, dg_merkle* tree, uint64_t* changed,
+                 uint64_t cap, dg_store* rows, dg_context* ctx_out, const dg_lww_diffs* diffs);
+int kd_finish_join(dg_engine* e, const KdArgs& p, const TreeScratch& ts, dg_store* state, dg_context* state_ctx,
+                   dg_store* spare, dg_merkle* tree, uint64_t* n_changed, int* swapped, dg_store* rows,
+                   dg_context* ctx_out, const char* what, u64* declined);
+
 // ---- api_fold.hip
 // dg_apply_deltas behind its argument checks: out <- the fold of the k deltas into (state, ctx)
 int apply_deltas(dg_engine* e, const dg_store* state, const dg_context* ctx, int k, const dg_store* deltas,

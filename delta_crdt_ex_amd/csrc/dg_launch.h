@@ -167,6 +167,11 @@ struct KsSeg {  // one keyset; the table ends with a sentinel {nullptr, M}
 // entries (device).
 hipError_t launch_keysets_gather(const KsSeg* segs, int k, u64 m, u64* cat, uint8_t* set, u32* bad,
                                  hipStream_t st);
+// skey / sset [0, m): the items ordered by (key, keyset) without a sort -- k lower bounds per
+// item over the (ascending) keysets -- for totals of a few thousand, m * k <= KS_RANK_MAX;
+// *bad |= 1 when a keyset is not strictly ascending (the output is then to be discarded).
+constexpr u64 KS_RANK_MAX = 1ull << 21;
+hipError_t launch_keysets_rank(const KsSeg* segs, int k, u64 m, u64* skey, uint8_t* sset, u32* bad, hipStream_t st);
 // The union of the m items in sorted order (item i is cat[idx[i]]; idx == nullptr: the
 // identity) and per union key the OR of 1 << set over its run: ukeys_d[0, m) always (device
 // scratch), ukeys / masks [0, cap) the first cap of them; *d_count = union keys.  Uses look-back
@@ -450,6 +455,25 @@ hipError_t launch_kd_join(const KdArgs& p, hipStream_t st);
 // kd_finish_kernel (merkle_build.hip): the write (dg_kdw.h) and, with a tree, its dirty chunks' re-reduction in one launch
 hipError_t launch_kd_finish(const KdArgs& p, const u32* dirty, u32* arrive, u64* hand, const i64* cdelta,
                             hipStream_t st);
+// dg_join_deltas_keyed: the fold of k keyed deltas (kfold.hip's rule per candidate tuple) as a
+// thread per key of the keysets' union.  kk_prep_kernel builds kfold_prep's VV tables and C_k;
+// kk_count_kernel is kd_count_kernel's counterpart: it writes each key's surviving NEW rows
+// into the edit store `e` and fills kd's per-key arrays with d = e, so that kd_finish_kernel
+// and splice_kernel run unchanged behind it.
+struct KkArgs {
+  KdArgs kd;           // keys = the union (ascending), d = the edit store, uc_* = C_k (the prep),
+                       //   cd and cu_tmp unused
+  const u64* masks;    // per union key: bit i set iff keyset i holds it
+  const KRun* runs;    // the k deltas (device; every keys != nullptr, every ctx a VV)
+  int k;
+  Ctx c0;              // the state's context (a VV)
+  u64 *tabC, *tabP;    // k x KNT each, zero on entry: c_i and C_{i-1} (the prep writes them)
+  RowsOut e;           // the edit store, e_rows rows: a key's new rows are contiguous, keys in
+  u64 e_rows;          //   no order; e_rows = Σ deltas[i].n exactly (the guard compares)
+  u64* e_next;         // its bump pointer, zero on entry
+  u32* flag;           // KF_PREP_FAIL: a node id >= KNT in a context (zero on entry)
+};
+hipError_t launch_kk_join(const KkArgs& q, hipStream_t st);
 
 // ---- small.hip: dg_join_delta of a small delta, one launch (see the file header)
 constexpr u32 SMALL_KEYS = 512, SMALL_DELTA = 512, SMALL_DCTX = 1024, SMALL_NODES = 2048;

@@ -4,7 +4,8 @@
 // The rows are then taken ONCE for the union by take.hip, whose per-key offsets say which
 // rows belong to which key and so, through the masks, to which message.
 //
-// Shape: (key, set) pairs through sort.hip's stable radix sort, then a run-detect pass.
+// Shape: (key, set) pairs through sort.hip's stable radix sort, then a run-detect pass.  (For a
+// few thousand items dg_join_deltas_keyed gets the sorted pairs from keysets_rank_kernel instead.)
 //
 //  1. keysets_gather_kernel lays the keysets end to end: cat[p] = the key, set[p] = its
 //     keyset (u8), and compares every key with its predecessor in its keyset in the same
@@ -61,6 +62,86 @@ __global__ __launch_bounds__(UB) void keysets_gather_kernel(const KsSeg* segs, i
     if (i > 0 && kj[i - 1] >= key) unordered = true;
     cat[p] = key;
     set[p] = (uint8_t)a;
+  }
+  if (unordered) atomicOr(bad, 1u);
+}
+
+// The same items in sorted order WITHOUT a sort, for a few thousand of them
+// (dg_join_deltas_keyed's small batches, where the radix sort's eight passes are latency, not
+// work): every keyset is ascending, so item (key x of keyset a) stands at
+//   pos = Σ_t |{y in K_t : y < x}| + |{t < a : x in K_t}|
+// among all items ordered by (key, keyset) -- k lower bounds per item, the searches of
+// RANK_G keysets interleaved so that their loads are in flight together.  skey[pos] = x,
+// sset[pos] = a: what the gather and the sort leave, with idx the identity.  A keyset that is
+// not strictly ascending sets *bad (its items' places are then not a permutation: a place past
+// the end is not written, and the caller discards the result).
+constexpr int RANK_G = 8;
+__global__ __launch_bounds__(UB) void keysets_rank_kernel(const KsSeg* segs, int k, u64 m, u64* skey, uint8_t* sset,
+                                                          u32* bad) {
+  __shared__ const u64* s_keys[KS_MAX_K];
+  __shared__ u64 s_off[KS_MAX_K + 1];
+  for (int j = threadIdx.x; j <= k; j += UB) {
+    if (j < k) s_keys[j] = segs[j].keys;
+    s_off[j] = segs[j].off;
+  }
+  __syncthreads();
+  const u64 p = (u64)blockIdx.x * UB + threadIdx.x;
+  if (p >= m) return;
+  int a = 0, b = k;  // the last keyset j with s_off[j] <= p (empty keysets share an offset)
+  while (b - a > 1) {
+    const int mid = (a + b) >> 1;
+    if (s_off[mid] <= p)
+      a = mid;
+    else
+      b = mid;
+  }
+  const u64 i = p - s_off[a];
+  const u64 x = s_keys[a][i];
+  bool unordered = i > 0 && s_keys[a][i - 1] >= x;
+  u64 pos = 0;
+  for (int t0 = 0; t0 < k; t0 += RANK_G) {
+    u64 lo[RANK_G], len[RANK_G], n[RANK_G];
+    const u64* kt[RANK_G];
+    u64 busy = 0;
+#pragma unroll
+    for (int g = 0; g < RANK_G; g++) {
+      const int t = t0 + g < k ? t0 + g : t0;
+      kt[g] = s_keys[t];
+      n[g] = t0 + g < k ? s_off[t + 1] - s_off[t] : 0;
+      lo[g] = 0;
+      len[g] = n[g];
+      busy |= len[g];
+    }
+    while (busy) {  // one step of every search: the group's loads go out together
+      u64 v[RANK_G];
+#pragma unroll
+      for (int g = 0; g < RANK_G; g++) v[g] = len[g] ? kt[g][lo[g] + (len[g] >> 1)] : 0;
+      busy = 0;
+#pragma unroll
+      for (int g = 0; g < RANK_G; g++) {
+        const u64 half = len[g] >> 1;
+        if (len[g]) {
+          if (v[g] < x) {
+            lo[g] += half + 1;
+            len[g] -= half + 1;
+          } else {
+            len[g] = half;
+          }
+        }
+        busy |= len[g];
+      }
+    }
+    u64 eq[RANK_G];
+#pragma unroll
+    for (int g = 0; g < RANK_G; g++) eq[g] = (t0 + g < a && lo[g] < n[g]) ? kt[g][lo[g]] : ~x;
+#pragma unroll
+    for (int g = 0; g < RANK_G; g++) pos += lo[g] + (eq[g] == x ? 1u : 0u);
+  }
+  if (pos < m) {
+    skey[pos] = x;
+    sset[pos] = (uint8_t)a;
+  } else {
+    unordered = true;
   }
   if (unordered) atomicOr(bad, 1u);
 }
@@ -152,6 +233,13 @@ hipError_t launch_keysets_gather(const KsSeg* segs, int k, u64 m, u64* cat, uint
   u64 g = (m + UB * 4 - 1) / (UB * 4);
   g = g > 4096 ? 4096 : g;
   hipLaunchKernelGGL(keysets_gather_kernel, dim3((unsigned)g), dim3(UB), 0, st, segs, k, m, cat, set, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_keysets_rank(const KsSeg* segs, int k, u64 m, u64* skey, uint8_t* sset, u32* bad, hipStream_t st) {
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(keysets_rank_kernel, dim3((unsigned)((m + UB - 1) / UB)), dim3(UB), 0, st, segs, k, m, skey,
+                     sset, bad);
   return hipGetLastError();
 }
 

@@ -98,6 +98,7 @@ _SIGS = {
     "dgr_engine_open": (I32, [I32, C.POINTER(VP)]),
     "dgr_engine_close": (I32, [VP]),
     "dgr_live_states": (U64, [VP]),
+    "dgr_deltas_route_stats": (I32, [VP, PU64]),
     "dgr_dg": (VP, [VP]),
     "dgr_refresh_terms": (I32, [VP, VP, U64, VP, VP, U64]),
     "dgr_remap": (I32, [VP, VP, VP, U64]),
@@ -231,6 +232,16 @@ class Engine:
                 return ("error", (_abi.DG_E_INVAL, f"{unknown} rows hold a key id the table lacks"))
         return ("ok", U.sweep(used_v, used_k, keep_values=[self.unwrap(t) for t in keep_values],
                               keep_keys=[self.unwrap(t) for t in keep_keys]))
+
+    def deltas_route_stats(self):
+        """(tried, served, declined): how often this engine's join_deltas[_diffs] tried
+        dg_join_deltas_keyed, was served by it and was declined (dgr_deltas_route_stats; the
+        route is DGR_DELTAS_ROUTE at engine open).  Not a NIF function: tests and A/B."""
+        out = (C.c_uint64 * 3)()
+        rc = self.lib.dgr_deltas_route_stats(self.ptr, out)
+        if rc:
+            raise _abi.DeltaGpuError(rc, "dgr_deltas_route_stats failed")
+        return tuple(int(x) for x in out)
 
     def close(self):
         for s in self.states:

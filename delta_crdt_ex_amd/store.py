@@ -830,6 +830,26 @@ class Engine:
         delta the result lands in `spare` and the two Store objects exchange their columns;
         `spare` then holds the old rows (n = 0, as after join_delta).  Returns what
         join_delta_diffs returns: (changed keys, old_val, new_val, flags, swapped)."""
+        return self._join_batch(False, state, state_ctx, deltas, dctxs, keys, spare, tree, changed, rows, diffs,
+                                ctx_out, True)
+
+    def join_deltas_keyed(self, state: Store, state_ctx: Context, deltas, dctxs, keys, spare: Store,
+                          tree: MerkleTree | None = None, changed: torch.Tensor | None = None,
+                          rows: Store | None = None, diffs: _abi.dg_lww_diffs | None = None,
+                          ctx_out: Context | None = None, want_diffs: bool = True):
+        """join_deltas at the cost of the keys the batch names (dg_join_deltas_keyed): a thread
+        per key of the keysets' union, in place when every union key keeps its row count
+        (swapped False, `spare` untouched), else through `spare` as join_delta.  Returns
+        join_deltas' tuple, or None when the library declined (DG_KEYED_FALLBACK: nothing was
+        touched -- call join_deltas).  want_diffs=False: the library computes no diffs (the
+        three diff arrays of the tuple are None)."""
+        return self._join_batch(True, state, state_ctx, deltas, dctxs, keys, spare, tree, changed, rows, diffs,
+                                ctx_out, want_diffs)
+
+    def _join_batch(self, keyed, state, state_ctx, deltas, dctxs, keys, spare, tree, changed, rows, diffs,
+                    ctx_out, want_diffs):
+        """The marshalling join_deltas and join_deltas_keyed share, and the exchange of the
+        Store objects' columns behind the call."""
         self._order()
         k = len(deltas)
         arr_s = (_abi.dg_store * max(k, 1))(*[d.abi() for d in deltas])
@@ -850,26 +870,34 @@ class Engine:
             bound = sum(d.n for d in deltas) + (state.n if full else sum(int(t.numel()) for t in keys))
             changed = torch.empty(max(bound, 1), dtype=_I64, device=self.device)
         cap = int(changed.numel())
-        own = diffs is None
+        own = want_diffs and diffs is None
+        ov = nv = fl = None
+        d = diffs if want_diffs else None
         if own:
             ov, nv, fl, d = self._diffs(cap)
-        else:
-            ov = nv = fl = None
-            d = diffs
         ss, sc, sp = state.abi(), state_ctx.abi(), spare.abi()
         t = tree.abi() if tree is not None else None
         ro = rows.abi() if rows is not None else None
         co = ctx_out.abi() if ctx_out is not None else None
         n = C.c_uint64(0)
-        check(self.lib.dg_join_deltas(
-            self.h, C.byref(ss), C.byref(sc), k, arr_s, arr_c, kp, kn, C.byref(sp),
-            C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n),
-            C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None, C.byref(d)))
+        args = (self.h, C.byref(ss), C.byref(sc), k, arr_s, arr_c, kp, kn, C.byref(sp),
+                C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n),
+                C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None,
+                C.byref(d) if d is not None else None)
+        if keyed:
+            sw = C.c_int(0)
+            rc = self.lib.dg_join_deltas_keyed(*args, C.byref(sw))
+            if rc == _abi.DG_KEYED_FALLBACK:
+                return None
+            check(rc)
+            swapped = bool(sw.value)
+        else:
+            check(self.lib.dg_join_deltas(*args))
+            swapped = k > 0
         if rows is not None:
             rows.n = int(ro.n)
         if ctx_out is not None:
             ctx_out.n, ctx_out.kind = int(co.n), int(co.kind)
-        swapped = k > 0
         if swapped:
             for f in ("key", "val", "ts", "node", "cnt"):
                 a, b = getattr(state, f), getattr(spare, f)

@@ -446,6 +446,38 @@ int dg_join_deltas(dg_engine* e, dg_store* state, dg_context* state_ctx, int k, 
                    dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
                    uint64_t* n_changed, dg_store* rows, dg_context* ctx_out, dg_lww_diffs* diffs);
 
+/* dg_join_deltas for a batch of SMALL keyed deltas, at the cost of the keys the batch names:
+ * every key of the keysets' union is folded by a thread of its own (one search of the state
+ * per union key, the deltas' runs of the key, the fold's rule per candidate row) and no row
+ * outside the union is read -- unless rows move, when the untouched rows are copied once.
+ * The contract on state, state_ctx, tree, changed, rows, ctx_out and diffs is dg_join_deltas':
+ * the net changed keys ascending, the net LWW reads before and after the batch, the changed
+ * keys' rows, a tree bit-identical to a rebuild, all or nothing; the capacity errors and
+ * k == 0 are dg_join_deltas' too.  It differs in two ways:
+ *   *swapped  as dg_join_delta: 0 when every union key kept its row count -- the state was
+ *             joined in place and `spare` was not touched -- else 1: the joined state was
+ *             written to `spare` and the two dg_store structs were exchanged.  (A key of
+ *             several rows that loses one and gains one also goes through `spare`.)
+ *   return    DG_KEYED_FALLBACK (positive) for a batch this path does not serve, with the
+ *             state, its context and the tree untouched: the caller then makes the
+ *             dg_join_deltas call with the same arguments.
+ * A batch is served when 1 <= k <= 64; keys and every keys[i] are non-NULL (no full-state
+ * join) and some keyset is non-empty; state_ctx and every dctxs[i] is a version vector
+ * (DG_CTX_VV: a batch with a dot-set context falls back) whose node ids are all < 1024; every
+ * delta row's key lies in that delta's own keyset (found on the device: the rows of the
+ * keyset's keys must add up to deltas[i].n); no union key has more than 64 state rows, more
+ * than 64 rows in one delta, or more than 64 distinct delta rows over the batch; state and
+ * spare columns are 16-byte aligned as dg_store_alloc makes them.  A keyset that is not
+ * strictly ascending: DG_E_ORDER.  Two host waits, the union's size and the join; a third,
+ * the keysets' order before the sort, when the keysets hold more than 2^21 / k keys in all.
+ * Synchronous. */
+#define DG_KEYED_FALLBACK 3
+int dg_join_deltas_keyed(dg_engine* e, dg_store* state, dg_context* state_ctx, int k, const dg_store* deltas,
+                         const dg_context* dctxs, const uint64_t* const* keys, const uint64_t* n_keys,
+                         dg_store* spare, dg_merkle* tree, uint64_t* changed, uint64_t cap,
+                         uint64_t* n_changed, dg_store* rows, dg_context* ctx_out, dg_lww_diffs* diffs,
+                         int* swapped);
+
 /* ---- sync deltas ----------------------------------------------------------- */
 /* The value half of a sync delta, Map.take(state.value, keys) (causal_crdt.ex:112-123,
  * 324-335: {:diff, %{state | dots: diff.dots, value: Map.take(value, keys)}, keys}):

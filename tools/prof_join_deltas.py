@@ -11,11 +11,18 @@ outside every timed window; at least 5 rounds, min - max over the rounds:
     batch/r   dg_join_deltas with tree and diffs, the tree rebuilt   (DG_TREE_REBUILD=always)
     batch/u   dg_join_deltas with tree and diffs, the tree updated   (DG_TREE_REBUILD=never)
     seq       k sequential dg_join_delta_diffs
+    keyed     dg_join_deltas_keyed with tree and diffs (a thread per key of the keysets' union);
+              before timing its state, context, tree and changed keys are compared with batch/u's
 
-    python tools/prof_join_deltas.py                  # the table (--small: 1M / 1.25M keys)
+    python tools/prof_join_deltas.py                  # the table (--small: 1M / 1.25M keys;
+                                                      # --k 2,3,4,8,64: the batch sizes; --states 1:
+                                                      # the config-4-sized state alone)
     python tools/prof_join_deltas.py --trace 5        # 5 dg_join_deltas calls per tree mode on the
                                                       # config-3 shard, k = 64 x 1 %: the target of a
                                                       # kernel-trace run of its own
+    python tools/prof_join_deltas.py --trace-keyed 5  # 5 dg_join_deltas_keyed calls on the config-4-sized
+                                                      # state (12.5M keys; with --small 1.25M, as DESIGN 4.17's
+                                                      # split), k = 64 x 200 keys: the same for the keyed call
 """
 import argparse
 import os
@@ -108,8 +115,31 @@ def variants(sh, eng_r, eng_u):
         for d, c, k in zip(sh.ds, sh.dcs, sh.ks):
             eng_r.join_delta_diffs(sh.st, sh.ctx, d, c, k, sh.spare, sh.tree, changed=sh.changed)
 
+    def keyed():
+        got = eng_u.join_deltas_keyed(sh.st, sh.ctx, sh.ds, sh.dcs, sh.ks, sh.spare, sh.tree, changed=sh.changed)
+        assert got is not None, "dg_join_deltas_keyed declined the batch"
+        return got
+
     return [("fold", eng_r, fold), ("sdiff", eng_r, sdiff), ("batch/r", eng_r, batch(eng_r)),
-            ("batch/u", eng_u, batch(eng_u)), ("seq", eng_r, seq)]
+            ("batch/u", eng_u, batch(eng_u)), ("seq", eng_r, seq), ("keyed", eng_u, keyed)]
+
+
+def same_results(sh, a, b):
+    """variants a and b leave the same state, context, tree and changed keys (and say whether
+    the keyed call moved rows)"""
+    got = []
+    for fn in (a, b):
+        sh.restore()
+        ch, ov, nv, fl, sw = fn()
+        torch.cuda.synchronize()
+        n = sh.st.n
+        got.append(([getattr(sh.st, f)[:n].clone() for f in COLS], sh.ctx.node[:sh.ctx.n].clone(),
+                    sh.ctx.cnt[:sh.ctx.n].clone(), sh.tree.nodes.clone(), sh.tree.counts.clone(), sh.tree.n_keys,
+                    ch.clone(), ov.clone(), nv.clone(), fl.clone()))
+    x, y = got
+    assert all(torch.equal(p, q) for p, q in zip(x[0], y[0])) and x[5] == y[5]
+    assert all(torch.equal(p, q) for p, q in zip(x[1:5] + x[6:], y[1:5] + y[6:]))
+    return sw
 
 
 def main():
@@ -117,6 +147,9 @@ def main():
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--trace-keyed", type=int, default=0)
+    ap.add_argument("--k", default="2,8,64")
+    ap.add_argument("--states", default="0,1", help="which of the two states: 0 the config-3 shard, 1 the config-4-sized")
     a = ap.parse_args()
     eng_r, eng_u = engine("always"), engine("never")
     print("build digest", eng_r.lib.dg_build_digest().decode(), "device", torch.cuda.get_device_name(0))
@@ -132,13 +165,23 @@ def main():
                 ch, *_ = eng.join_deltas(sh.st, sh.ctx, sh.ds, sh.dcs, sh.ks, sh.spare, sh.tree, changed=sh.changed)
             print(f"{a.trace} dg_join_deltas calls, tree {name}: {ch.numel()} changed keys of {n}")
         return
+    if a.trace_keyed:  # (the config-4-sized state, 64 x 200 keys: the target of a kernel-trace run of its own)
+        n = sizes[1][1]
+        base, deltas = W.config3(n_keys=n, n_replicas=64, touch=200 / n)
+        sh = Shape(eng_u, base, deltas)
+        for _ in range(a.trace_keyed):
+            sh.restore()
+            ch, *_ = eng_u.join_deltas_keyed(sh.st, sh.ctx, sh.ds, sh.dcs, sh.ks, sh.spare, sh.tree, changed=sh.changed)
+        print(f"{a.trace_keyed} dg_join_deltas_keyed calls: {ch.numel()} changed keys of {n}")
+        return
     rounds = max(a.rounds, 5)
-    for sname, n in sizes:
+    for sname, n in (sizes[int(i)] for i in a.states.split(",")):
         for touch, tname in ((200 / n, "200 keys"), (0.01, "1 % of the keys")):
             base, all_deltas = W.config3(n_keys=n, n_replicas=64, touch=touch)
-            for k in (2, 8, 64):
+            for k in (int(x) for x in a.k.split(",")):
                 sh = Shape(eng_r, base, all_deltas[:k])
                 vs = variants(sh, eng_r, eng_u)
+                moved = same_results(sh, vs[3][2], vs[5][2])
                 t = {name: [] for name, _, _ in vs}
                 n_changed = 0
                 for r in range(rounds + 1):  # (round 0 warms the scratch buffers up)
@@ -155,6 +198,7 @@ def main():
                     print(f"   {name:8s} {v.min():10.1f} - {v.max():10.1f}  ({np.median(v):10.1f})")
                 f, b = np.median(t["fold"]), min(np.median(t["batch/r"]), np.median(t["batch/u"]))
                 print(f"   post-pass over the plain fold: {b - f:.1f} us; batch / seq = {b / np.median(t['seq']):.3f}")
+                print(f"   keyed == batch/u byte for byte; rows {'moved through the spare store' if moved else 'joined in place'}")
                 del sh
                 torch.cuda.empty_cache()
     eng_r.close()
