@@ -63,6 +63,20 @@ def _callback_diffs(U, order, changed, old_val, new_val, flags):
     return diffs
 
 
+def _make_room(state: M.AWLWWMap, spare: Store, n_ctx: int, n_rows: int):
+    """Room in the resident state's context for `n_ctx` more entries and in `spare` for the
+    state's rows plus `n_rows`: both grow by doubling what the join needs."""
+    rows, ctx = state.rows, state.ctx
+    need = ctx.n + n_ctx
+    if ctx.cap < need:  # room for the union (a resident replica's context grows by doubling)
+        grown = Context.empty(ctx.kind, 2 * need, rows.device)
+        grown.node[: ctx.n].copy_(ctx.node[: ctx.n])
+        grown.cnt[: ctx.n].copy_(ctx.cnt[: ctx.n])
+        ctx.node, ctx.cnt = grown.node, grown.cnt
+    if spare.cap < rows.n + n_rows:  # (the spare holds no rows: nothing to copy)
+        spare.swap_columns(Store.empty(2 * (rows.n + n_rows), rows.device))
+
+
 def update_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys):
     """Returns (new_state, diffs): diffs is what on_diffs would receive -- None when no
     key's value map changed (diffs_to_callback/3 is not reached), else a list of
@@ -93,16 +107,7 @@ def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys,
     order, kt = _keyset(U, keys)
     eng = M.engine()
     rows, ctx = state.rows, state.ctx
-    need = ctx.n + delta.ctx.n
-    if ctx.cap < need:  # room for the union (a resident replica's context grows by doubling)
-        grown = Context.empty(ctx.kind, 2 * need, rows.device)
-        grown.node[: ctx.n].copy_(ctx.node[: ctx.n])
-        grown.cnt[: ctx.n].copy_(ctx.cnt[: ctx.n])
-        ctx.node, ctx.cnt = grown.node, grown.cnt
-    if spare.cap < rows.n + delta.rows.n:
-        grown = Store.empty(2 * (rows.n + delta.rows.n), rows.device)
-        for f in ("key", "val", "ts", "node", "cnt"):
-            setattr(spare, f, getattr(grown, f))
+    _make_room(state, spare, delta.ctx.n, delta.rows.n)
     home = None
     if kt.numel() <= HOME_KEYS and delta.rows.n <= HOME_ROWS and delta.ctx.n <= HOME_CTX:
         # a mutation or a small sync delta: the one-launch join gives the diffs too
@@ -146,17 +151,7 @@ def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tr
     if not batch:
         return None
     rows, ctx = state.rows, state.ctx
-    need = ctx.n + sum(d.ctx.n for d, _ in batch)
-    if ctx.cap < need:  # room for the union (a resident replica's context grows by doubling)
-        grown = Context.empty(ctx.kind, 2 * need, rows.device)
-        grown.node[: ctx.n].copy_(ctx.node[: ctx.n])
-        grown.cnt[: ctx.n].copy_(ctx.cnt[: ctx.n])
-        ctx.node, ctx.cnt = grown.node, grown.cnt
-    need_rows = rows.n + sum(d.rows.n for d, _ in batch)
-    if spare.cap < need_rows:
-        grown = Store.empty(2 * need_rows, rows.device)
-        for f in ("key", "val", "ts", "node", "cnt"):
-            setattr(spare, f, getattr(grown, f))
+    _make_room(state, spare, sum(d.ctx.n for d, _ in batch), sum(d.rows.n for d, _ in batch))
     state._host = None
     args = (rows, ctx, [d.rows for d, _ in batch], [d.ctx for d, _ in batch], kts, spare, tree)
     # the fold per key of the keysets' union where the library serves the batch (VV contexts,

@@ -27,6 +27,11 @@ def _ptr(t: torch.Tensor | None, ctype):
     return C.cast(C.c_void_p(t.data_ptr()), ctype)
 
 
+def _ref(x):
+    """byref of an optional ABI struct: None stays NULL."""
+    return C.byref(x) if x is not None else None
+
+
 def _np_to_dev(a: np.ndarray, dtype_view, device) -> torch.Tensor:
     a = np.ascontiguousarray(a).view(dtype_view)
     return torch.from_numpy(a.copy()).to(device, non_blocking=False)
@@ -91,6 +96,17 @@ class Store:
         return _abi.dg_store(self.key.data_ptr(), self.val.data_ptr(), self.ts.data_ptr(),
                              self.node.data_ptr(), self.cnt.data_ptr(), self.n, self.cap)
 
+    def _set(self, s: _abi.dg_store):
+        """Take back what a call wrote into this store's struct: its row count."""
+        self.n = int(s.n)
+
+    def swap_columns(self, other: "Store"):
+        """Exchange the five column tensors with `other` (the counts stay where they are)."""
+        for f in ("key", "val", "ts", "node", "cnt"):
+            a, b = getattr(self, f), getattr(other, f)
+            setattr(self, f, b)
+            setattr(other, f, a)
+
 
 @dataclass
 class Context:
@@ -126,6 +142,10 @@ class Context:
     def abi(self) -> _abi.dg_context:
         return _abi.dg_context(self.kind, 0, self.node.data_ptr(), self.cnt.data_ptr(), self.n,
                                self.cap)
+
+    def _set(self, c: _abi.dg_context):
+        """Take back what a call wrote into this context's struct: its count and kind."""
+        self.n, self.kind = int(c.n), int(c.kind)
 
 
 class TermHashes:
@@ -335,21 +355,58 @@ class Engine:
             return _ptr(self._no_keys, _abi.P64), 0
         return _ptr(keys, _abi.P64), int(keys.numel())
 
+    def _keysets(self, keys):
+        """(kp, kn, keepalive) of a list of keysets -- the `void*[k]` and `uint64[k]` pair of
+        the batch calls: None for the whole list -> NULL, NULL; an element goes by `_keys`'
+        rule (None: every key; an empty tensor: a join or take over no key, not a full-state
+        one).  `keepalive` owns the memory `kn` points into and the keysets themselves."""
+        if keys is None:
+            return None, None, ()
+        ptrs = [C.cast(self._keys(t)[0], C.c_void_p) if t is not None else None for t in keys]
+        kp = (C.c_void_p * max(len(keys), 1))(*ptrs)
+        kn_np = np.array([int(t.numel()) if t is not None else 0 for t in keys] or [0], np.uint64)
+        return kp, kn_np.ctypes.data_as(_abi.P64), (kn_np, keys)
+
+    @staticmethod
+    def _structs(items, ctype):
+        """The `ctype[k]` array of the ABI structs of k stores or contexts (k = 0: one zeroed
+        element, so that the array has an address)."""
+        return (ctype * max(len(items), 1))(*[x.abi() for x in items])
+
+    def _outputs(self, out, out_ctx, n_rows, n_ctx):
+        """A join's outputs: the caller's, or fresh ones of the given sizes."""
+        if out is None:
+            out = Store.empty(n_rows, self.device)
+        if out_ctx is None:
+            out_ctx = Context.empty(DG_CTX_VV, n_ctx, self.device)
+        return out, out_ctx
+
+    @staticmethod
+    def _commit_join(state, state_ctx, spare, tree, ss, sc, t, swapped):
+        """What every resident join does behind the library's call: when the result landed
+        in `spare`, the two Store objects exchange their columns (`state` always holds the
+        joined rows, `spare` the old ones with n = 0); the counts come back from the structs
+        and `tree` indexes `state`."""
+        if swapped:
+            state.swap_columns(spare)
+            spare.n = 0
+        state._set(ss)
+        state_ctx._set(sc)
+        if tree is not None:
+            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
+            tree.store = state
+
     def join2(self, a: Store, ca: Context, b: Store, cb: Context, keys: torch.Tensor | None = None,
               out: Store | None = None, out_ctx: Context | None = None):
         self._order()
-        if out is None:
-            out = Store.empty(a.n + b.n, self.device)
-        if out_ctx is None:
-            out_ctx = Context.empty(DG_CTX_VV, ca.n + cb.n, self.device)
+        out, out_ctx = self._outputs(out, out_ctx, a.n + b.n, ca.n + cb.n)
         so, co = out.abi(), out_ctx.abi()
         sa, sb, xa, xb = a.abi(), b.abi(), ca.abi(), cb.abi()
         kp, nk = self._keys(keys)
         check(self.lib.dg_join2(self.h, C.byref(sa), C.byref(xa), C.byref(sb), C.byref(xb),
                                 kp, nk, C.byref(so), C.byref(co)))
-        out.n = int(so.n)
-        out_ctx.n = int(co.n)
-        out_ctx.kind = int(co.kind)
+        out._set(so)
+        out_ctx._set(co)
         return out, out_ctx
 
     def join2_changes(self, a: Store, ca: Context, b: Store, cb: Context,
@@ -359,10 +416,7 @@ class Engine:
         returns (out, out_ctx, changed) with `changed` the ascending device int64 tensor
         of the keys (of `keys`, or all) whose rows in `out` differ from those in `a`."""
         self._order()
-        if out is None:
-            out = Store.empty(a.n + b.n, self.device)
-        if out_ctx is None:
-            out_ctx = Context.empty(DG_CTX_VV, ca.n + cb.n, self.device)
+        out, out_ctx = self._outputs(out, out_ctx, a.n + b.n, ca.n + cb.n)
         cap = max(a.n + b.n, 1)
         changed = torch.empty(cap, dtype=_I64, device=self.device)
         so, co = out.abi(), out_ctx.abi()
@@ -372,9 +426,8 @@ class Engine:
         check(self.lib.dg_join2_changes(self.h, C.byref(sa), C.byref(xa), C.byref(sb), C.byref(xb),
                                         kp, nk, C.byref(so), C.byref(co), _ptr(changed, _abi.P64),
                                         cap, C.byref(n)))
-        out.n = int(so.n)
-        out_ctx.n = int(co.n)
-        out_ctx.kind = int(co.kind)
+        out._set(so)
+        out_ctx._set(co)
         return out, out_ctx, changed[: n.value]
 
     def join2_async(self, a: Store, ca: Context, b: Store, cb: Context, out: Store,
@@ -412,17 +465,12 @@ class Engine:
     def joink(self, stores, ctxs, out: Store | None = None, out_ctx: Context | None = None):
         self._order()
         k = len(stores)
-        arr_s = (_abi.dg_store * k)(*[s.abi() for s in stores])
-        arr_c = (_abi.dg_context * k)(*[c.abi() for c in ctxs])
-        if out is None:
-            out = Store.empty(sum(s.n for s in stores), self.device)
-        if out_ctx is None:
-            out_ctx = Context.empty(DG_CTX_VV, sum(c.n for c in ctxs), self.device)
+        arr_s, arr_c = self._structs(stores, _abi.dg_store), self._structs(ctxs, _abi.dg_context)
+        out, out_ctx = self._outputs(out, out_ctx, sum(s.n for s in stores), sum(c.n for c in ctxs))
         so, co = out.abi(), out_ctx.abi()
         check(self.lib.dg_joink(self.h, k, arr_s, arr_c, C.byref(so), C.byref(co)))
-        out.n = int(so.n)
-        out_ctx.n = int(co.n)
-        out_ctx.kind = int(co.kind)
+        out._set(so)
+        out_ctx._set(co)
         return out, out_ctx
 
     def prepare_apply_deltas(self, state: Store, ctx: Context, deltas, dctxs, keys, out: Store,
@@ -431,15 +479,8 @@ class Engine:
         replica re-applying the same batch shape): returns a zero-argument callable that
         runs it and returns (out, out_ctx)."""
         k = len(deltas)
-        arr_s = (_abi.dg_store * max(k, 1))(*[d.abi() for d in deltas])
-        arr_c = (_abi.dg_context * max(k, 1))(*[c.abi() for c in dctxs])
-        kp = kn = None
-        if keys is not None:
-            ptrs = [self._keys(t)[0] if t is not None else None for t in keys]
-            kp = (C.c_void_p * max(k, 1))(*[C.cast(x, C.c_void_p) if x is not None else None
-                                           for x in ptrs])
-            kn_np = np.array([int(t.numel()) if t is not None else 0 for t in keys] or [0], np.uint64)
-            kn = kn_np.ctypes.data_as(_abi.P64)
+        arr_s, arr_c = self._structs(deltas, _abi.dg_store), self._structs(dctxs, _abi.dg_context)
+        kp, kn, keep = self._keysets(keys)
         ss, xs, so, co = state.abi(), ctx.abi(), out.abi(), out_ctx.abi()
         refs = (C.byref(ss), C.byref(xs), C.byref(so), C.byref(co))
         f, h = self.lib.dg_apply_deltas, self.h
@@ -452,9 +493,7 @@ class Engine:
             out_ctx.kind = int(co.kind)
             return out, out_ctx
 
-        run._keep = (arr_s, arr_c, kp, kn, keys, ss, xs, so, co, state, ctx, deltas, dctxs)
-        if keys is not None:
-            run._keep += (kn_np,)
+        run._keep = (arr_s, arr_c, kp, kn, keep, ss, xs, so, co, state, ctx, deltas, dctxs)
         return run
 
     def apply_deltas(self, state: Store, ctx: Context, deltas, dctxs, keys=None,
@@ -462,34 +501,9 @@ class Engine:
         """CausalCrdt's delta application (causal_crdt.ex:383-384): fold of
         join(state, deltas[i], keys[i]); keys[i] a sorted unique device int64 tensor of
         key ids, or None for a full-state join of that delta."""
-        self._order()
-        k = len(deltas)
-        arr_s = (_abi.dg_store * max(k, 1))(*[d.abi() for d in deltas])
-        arr_c = (_abi.dg_context * max(k, 1))(*[c.abi() for c in dctxs])
-        kp = kn = None
-        if keys is not None:
-            kp = (C.c_void_p * max(k, 1))(*[C.c_void_p(t.data_ptr() if t is not None and t.numel()
-                                                         else 0) for t in keys])
-            kn_np = np.array([int(t.numel()) if t is not None else 0 for t in keys] or [0],
-                             np.uint64)
-            kn = kn_np.ctypes.data_as(_abi.P64)
-            # an empty keyset is a join over no keys, not a full-state join: point it at
-            # a one-element dummy with n_keys = 0
-            dummy = torch.zeros(1, dtype=_I64, device=self.device)
-            for i, t in enumerate(keys):
-                if t is not None and t.numel() == 0:
-                    kp[i] = C.c_void_p(dummy.data_ptr())
-        if out is None:
-            out = Store.empty(state.n + sum(d.n for d in deltas), self.device)
-        if out_ctx is None:
-            out_ctx = Context.empty(DG_CTX_VV, ctx.n + sum(c.n for c in dctxs), self.device)
-        ss, xs, so, co = state.abi(), ctx.abi(), out.abi(), out_ctx.abi()
-        check(self.lib.dg_apply_deltas(self.h, C.byref(ss), C.byref(xs), k, arr_s, arr_c, kp, kn,
-                                       C.byref(so), C.byref(co)))
-        out.n = int(so.n)
-        out_ctx.n = int(co.n)
-        out_ctx.kind = int(co.kind)
-        return out, out_ctx
+        out, out_ctx = self._outputs(out, out_ctx, state.n + sum(d.n for d in deltas),
+                                     ctx.n + sum(c.n for c in dctxs))
+        return self.prepare_apply_deltas(state, ctx, deltas, dctxs, keys, out, out_ctx)()
 
     def take_keys(self, s: Store, keys: torch.Tensor, out: Store | None = None) -> Store:
         """Map.take(value, keys) of a sync delta (causal_crdt.ex:324-335): the rows of `s`
@@ -512,7 +526,7 @@ class Engine:
         else:
             so = out.abi()
             check(self.lib.dg_take_keys(self.h, C.byref(ss), kp, nk, C.byref(so)))
-        out.n = int(so.n)
+        out._set(so)
         return out
 
     def take_keysets(self, s: Store, keysets, out: Store | None = None, cap_keys: int | None = None):
@@ -527,12 +541,8 @@ class Engine:
         then carries the needed sizes as `.n_ukeys` and `.n_rows`."""
         self._order()
         k = len(keysets)
-        dummy = self._keys(torch.zeros(0, dtype=_I64, device=self.device))[0]
-        kp = (C.c_void_p * max(k, 1))(*[C.c_void_p(t.data_ptr()) if t.numel() else C.cast(dummy, C.c_void_p)
-                                       for t in keysets])
-        kn_np = np.array([int(t.numel()) for t in keysets] or [0], np.uint64)
-        kn = kn_np.ctypes.data_as(_abi.P64)
-        m = int(kn_np.sum())
+        kp, kn, _keep = self._keysets(keysets)
+        m = sum(int(t.numel()) for t in keysets)
         own_out, own_cap = out is None, cap_keys is None
         ss = s.abi()
         for attempt in range(2):
@@ -562,7 +572,7 @@ class Engine:
                     raise
             check(rc)
             break
-        out.n = int(so.n)
+        out._set(so)
         n = int(nu.value)
         return ukeys[:n], masks[:n], offs[:n + 1], out
 
@@ -590,9 +600,8 @@ class Engine:
             if rc != _abi.DG_E_CAPACITY:
                 break
         check(rc)
-        out.n = int(so.n)
-        dots.n = int(xd.n)
-        dots.kind = int(xd.kind)
+        out._set(so)
+        dots._set(xd)
         return out, dots, keys[: nk.value]
 
     # ---------------------------------------------------------------- contexts
@@ -602,8 +611,7 @@ class Engine:
             out = Context.empty(DG_CTX_VV, a.n + b.n, self.device)
         xa, xb, xo = a.abi(), b.abi(), out.abi()
         check(self.lib.dg_context_union(self.h, C.byref(xa), C.byref(xb), C.byref(xo)))
-        out.n = int(xo.n)
-        out.kind = int(xo.kind)
+        out._set(xo)
         return out
 
     def compress_dots(self, dots: Context, out: Context | None = None) -> Context:
@@ -612,8 +620,7 @@ class Engine:
             out = Context.empty(DG_CTX_VV, dots.n, self.device)
         xa, xo = dots.abi(), out.abi()
         check(self.lib.dg_compress_dots(self.h, C.byref(xa), C.byref(xo)))
-        out.n = int(xo.n)
-        out.kind = int(xo.kind)
+        out._set(xo)
         return out
 
     # ---------------------------------------------------------------- read
@@ -683,26 +690,14 @@ class Engine:
         n = C.c_uint64(0)
         sw = C.c_int(0)
         args = (self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp),
-                C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), int(changed.numel()),
-                C.byref(n), C.byref(sw))
+                _ref(t), _ptr(changed, _abi.P64), int(changed.numel()), C.byref(n), C.byref(sw))
         if rows is None:
             check(self.lib.dg_join_delta(*args))
         else:
             ro = rows.abi()
             check(self.lib.dg_join_delta_rows(*args, C.byref(ro)))
-            rows.n = int(ro.n)
-        if sw.value:
-            for f in ("key", "val", "ts", "node", "cnt"):
-                a, b = getattr(state, f), getattr(spare, f)
-                setattr(state, f, b)
-                setattr(spare, f, a)
-            spare.n = 0
-        state.n = int(ss.n)
-        state_ctx.n = int(sc.n)
-        state_ctx.kind = int(sc.kind)
-        if tree is not None:
-            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
-            tree.store = state
+            rows._set(ro)
+        self._commit_join(state, state_ctx, spare, tree, ss, sc, t, sw.value)
         return changed[: n.value], bool(sw.value)
 
     def _diffs(self, cap: int):
@@ -755,23 +750,12 @@ class Engine:
         sw = C.c_int(0)
         check(self.lib.dg_join_delta_diffs(
             self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp),
-            C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n), C.byref(sw),
-            C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None, C.byref(d)))
+            _ref(t), _ptr(changed, _abi.P64), cap, C.byref(n), C.byref(sw), _ref(ro), _ref(co), C.byref(d)))
         if rows is not None:
-            rows.n = int(ro.n)
+            rows._set(ro)
         if ctx_out is not None:
-            ctx_out.n, ctx_out.kind = int(co.n), int(co.kind)
-        if sw.value:
-            for f in ("key", "val", "ts", "node", "cnt"):
-                a, b = getattr(state, f), getattr(spare, f)
-                setattr(state, f, b)
-                setattr(spare, f, a)
-        state.n = int(ss.n)
-        state_ctx.n = int(sc.n)
-        state_ctx.kind = int(sc.kind)
-        if tree is not None:
-            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
-            tree.store = state
+            ctx_out._set(co)
+        self._commit_join(state, state_ctx, spare, tree, ss, sc, t, sw.value)
         nch = int(n.value)
         if own and d.cap == 0 and nch:
             # the gather behind a committed join failed (deltagpu.h): the old rows survive
@@ -779,9 +763,8 @@ class Engine:
             if not sw.value:
                 raise _abi.DeltaGpuError(_abi.DG_E_DEVICE, "the join applied, but its diffs were not "
                                          "gathered and the old rows are overwritten")
-            spare.n = int(sp.n)
+            spare.n = int(sp.n)  # the old rows count again while they are read
             ov, nv, fl = self.read_diff(spare, state, changed[:nch])
-        if sw.value:
             spare.n = 0
         if not own:
             return changed[:nch], None, None, None, bool(sw.value)
@@ -806,12 +789,11 @@ class Engine:
         so, sn = old.abi(), new.abi()
         n = C.c_uint64(0)
         check(self.lib.dg_store_diff(self.h, C.byref(so), C.byref(sn), _ptr(changed, _abi.P64), cap, C.byref(n),
-                                     C.byref(ro) if ro is not None else None,
-                                     C.byref(d) if want_diffs else None))
+                                     _ref(ro), C.byref(d) if want_diffs else None))
         nch = int(n.value)
         out = [changed[:nch]]
         if want_rows:
-            rows.n = int(ro.n)
+            rows._set(ro)
             if rows.n > rows.cap:
                 raise _abi.CapacityError(_abi.DG_E_CAPACITY, f"store_diff: {rows.n} rows > cap {rows.cap}")
             out.append(rows)
@@ -848,23 +830,12 @@ class Engine:
 
     def _join_batch(self, keyed, state, state_ctx, deltas, dctxs, keys, spare, tree, changed, rows, diffs,
                     ctx_out, want_diffs):
-        """The marshalling join_deltas and join_deltas_keyed share, and the exchange of the
-        Store objects' columns behind the call."""
+        """The marshalling join_deltas and join_deltas_keyed share, and the commit behind the
+        call (`_commit_join`)."""
         self._order()
         k = len(deltas)
-        arr_s = (_abi.dg_store * max(k, 1))(*[d.abi() for d in deltas])
-        arr_c = (_abi.dg_context * max(k, 1))(*[c.abi() for c in dctxs])
-        kp = kn = None
-        if keys is not None:
-            kp = (C.c_void_p * max(k, 1))(*[C.c_void_p(t.data_ptr() if t is not None and t.numel()
-                                                         else 0) for t in keys])
-            kn_np = np.array([int(t.numel()) if t is not None else 0 for t in keys] or [0], np.uint64)
-            kn = kn_np.ctypes.data_as(_abi.P64)
-            # (an empty keyset is a join over no keys, not a full-state join: see apply_deltas)
-            dummy = torch.zeros(1, dtype=_I64, device=self.device)
-            for i, t in enumerate(keys):
-                if t is not None and t.numel() == 0:
-                    kp[i] = C.c_void_p(dummy.data_ptr())
+        arr_s, arr_c = self._structs(deltas, _abi.dg_store), self._structs(dctxs, _abi.dg_context)
+        kp, kn, _keep = self._keysets(keys)
         if changed is None:
             full = keys is None or any(t is None for t in keys)
             bound = sum(d.n for d in deltas) + (state.n if full else sum(int(t.numel()) for t in keys))
@@ -880,10 +851,8 @@ class Engine:
         ro = rows.abi() if rows is not None else None
         co = ctx_out.abi() if ctx_out is not None else None
         n = C.c_uint64(0)
-        args = (self.h, C.byref(ss), C.byref(sc), k, arr_s, arr_c, kp, kn, C.byref(sp),
-                C.byref(t) if t is not None else None, _ptr(changed, _abi.P64), cap, C.byref(n),
-                C.byref(ro) if ro is not None else None, C.byref(co) if co is not None else None,
-                C.byref(d) if d is not None else None)
+        args = (self.h, C.byref(ss), C.byref(sc), k, arr_s, arr_c, kp, kn, C.byref(sp), _ref(t),
+                _ptr(changed, _abi.P64), cap, C.byref(n), _ref(ro), _ref(co), _ref(d))
         if keyed:
             sw = C.c_int(0)
             rc = self.lib.dg_join_deltas_keyed(*args, C.byref(sw))
@@ -895,21 +864,10 @@ class Engine:
             check(self.lib.dg_join_deltas(*args))
             swapped = k > 0
         if rows is not None:
-            rows.n = int(ro.n)
+            rows._set(ro)
         if ctx_out is not None:
-            ctx_out.n, ctx_out.kind = int(co.n), int(co.kind)
-        if swapped:
-            for f in ("key", "val", "ts", "node", "cnt"):
-                a, b = getattr(state, f), getattr(spare, f)
-                setattr(state, f, b)
-                setattr(spare, f, a)
-            spare.n = 0
-        state.n = int(ss.n)
-        state_ctx.n = int(sc.n)
-        state_ctx.kind = int(sc.kind)
-        if tree is not None:
-            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
-            tree.store = state
+            ctx_out._set(co)
+        self._commit_join(state, state_ctx, spare, tree, ss, sc, t, swapped)
         nch = int(n.value)
         if not own:
             return changed[:nch], None, None, None, swapped
@@ -940,8 +898,8 @@ class Engine:
         kp, nk = self._keys(keys)
         sw = C.c_int(0)
         f = self.lib.dg_join_delta_home_diffs if _diffs else self.lib.dg_join_delta_home
-        check(f(self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp),
-                C.byref(t) if t is not None else None, self._home, C.byref(sw)))
+        check(f(self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp), _ref(t),
+                self._home, C.byref(sw)))
         if int(h[0]) & _abi.DG_HOME_FALLBACK:
             return None
         nch, nr, nc = int(h[1]), int(h[2]), int(h[3])
@@ -953,18 +911,7 @@ class Engine:
         C0 = _abi.DG_HOME_CTX
         ctx = (h[C0 + _abi.DG_HOME_NODES:C0 + 2 * _abi.DG_HOME_NODES].view(np.uint32)[:nc].copy(),
                h[C0:C0 + nc].copy())
-        if sw.value:
-            for f in ("key", "val", "ts", "node", "cnt"):
-                a, b = getattr(state, f), getattr(spare, f)
-                setattr(state, f, b)
-                setattr(spare, f, a)
-            spare.n = 0
-        state.n = int(ss.n)
-        state_ctx.n = int(sc.n)
-        state_ctx.kind = int(sc.kind)
-        if tree is not None:
-            tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
-            tree.store = state
+        self._commit_join(state, state_ctx, spare, tree, ss, sc, t, sw.value)
         return keys_out, rows, ctx, bool(sw.value)
 
     def join_delta_home_diffs(self, state: Store, state_ctx: Context, delta: Store, delta_ctx: Context,
@@ -1041,10 +988,17 @@ class Engine:
         cont._set(c)
         return cont
 
-    def merkle_continue(self, tree: MerkleTree, cont: MerkleCont, levels: int = 8,
-                        cap: int | None = None):
-        """MerkleMap.continue_partial_diff(cont, mm, levels) (causal_crdt.ex:96) on this
-        replica's tree: ("continue", MerkleCont) or ("ok", keys, total)."""
+    @staticmethod
+    def _cont_sizes(cont: MerkleCont, max_entries):
+        """The (entries, buckets) a hop's output continuation is first given."""
+        oc, ob = 4 * max(cont.n, 1), max(cont.n, 1)
+        if max_entries is not None:
+            oc = min(oc, max(int(max_entries), 1))
+        return oc, ob
+
+    def _hop(self, home, tree, cont, levels, max_entries, cap):
+        """The body of merkle_continue and (home) merkle_continue_home: the call, run again
+        with the output continuation grown to the sizes a DG_E_CAPACITY answer reports."""
         self._order()
         s = tree.store
         if cap is None:
@@ -1052,22 +1006,31 @@ class Engine:
         keys = torch.empty(max(int(cap), 1), dtype=_I64, device=self.device)
         cin = cont.abi()
         t, ss = tree.abi(), s.abi()
-        out_cap, out_bcap = 4 * max(cont.n, 1), max(cont.n, 1)
+        mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
+        f, extra = (self.lib.dg_merkle_continue_home, (mx,)) if home else (self.lib.dg_merkle_continue, ())
+        out_cap, out_bcap = self._cont_sizes(cont, max_entries)
         for _ in range(3):  # grow the output continuation to the sizes the call reports
             out = MerkleCont.empty(out_cap, out_bcap, self.device)
             co = out.abi()
             nk, tot, st = C.c_uint64(), C.c_uint64(), C.c_int()
-            rc = self.lib.dg_merkle_continue(self.h, C.byref(t), C.byref(ss), C.byref(cin), levels,
-                                             C.byref(co), _ptr(keys, _abi.P64), int(cap),
-                                             C.byref(nk), C.byref(tot), C.byref(st))
+            rc = f(self.h, C.byref(t), C.byref(ss), C.byref(cin), levels, *extra, C.byref(co),
+                   _ptr(keys, _abi.P64), int(cap), C.byref(nk), C.byref(tot), C.byref(st))
             if rc != _abi.DG_E_CAPACITY:
                 break
             out_cap, out_bcap = max(int(co.n), out_cap), max(int(co.n_buckets), out_bcap)
         check(rc)
+        if home and st.value == _abi.DG_CONT_DECLINED:
+            return ("declined",)
         if st.value == 1:
             out._set(co)
             return ("continue", out)
         return ("ok", keys[: nk.value], int(tot.value))
+
+    def merkle_continue(self, tree: MerkleTree, cont: MerkleCont, levels: int = 8,
+                        cap: int | None = None):
+        """MerkleMap.continue_partial_diff(cont, mm, levels) (causal_crdt.ex:96) on this
+        replica's tree: ("continue", MerkleCont) or ("ok", keys, total)."""
+        return self._hop(False, tree, cont, levels, None, cap)
 
     def merkle_continue_home(self, tree: MerkleTree, cont: MerkleCont, levels: int = 8,
                              max_entries: int | None = None, cap: int | None = None):
@@ -1075,34 +1038,7 @@ class Engine:
         max_entries; None: :infinite) in one launch with one host wait.  ("continue",
         MerkleCont), ("ok", keys, total), or ("declined",) for a continuation over the
         one-workgroup limits (then merkle_continue)."""
-        self._order()
-        s = tree.store
-        mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
-        if cap is None:
-            cap = max(cont.n, 1) + s.n
-        keys = torch.empty(max(int(cap), 1), dtype=_I64, device=self.device)
-        cin = cont.abi()
-        t, ss = tree.abi(), s.abi()
-        out_cap, out_bcap = 4 * max(cont.n, 1), max(cont.n, 1)
-        if max_entries is not None:
-            out_cap = min(out_cap, max(int(max_entries), 1))
-        for _ in range(3):
-            out = MerkleCont.empty(out_cap, out_bcap, self.device)
-            co = out.abi()
-            nk, tot, st = C.c_uint64(), C.c_uint64(), C.c_int()
-            rc = self.lib.dg_merkle_continue_home(self.h, C.byref(t), C.byref(ss), C.byref(cin), levels,
-                                                  mx, C.byref(co), _ptr(keys, _abi.P64), int(cap),
-                                                  C.byref(nk), C.byref(tot), C.byref(st))
-            if rc != _abi.DG_E_CAPACITY:
-                break
-            out_cap, out_bcap = max(int(co.n), out_cap), max(int(co.n_buckets), out_bcap)
-        check(rc)
-        if st.value == _abi.DG_CONT_DECLINED:
-            return ("declined",)
-        if st.value == 1:
-            out._set(co)
-            return ("continue", out)
-        return ("ok", keys[: nk.value], int(tot.value))
+        return self._hop(True, tree, cont, levels, max_entries, cap)
 
     def merkle_continues(self, tree: MerkleTree, conts, levels: int = 8, max_entries: int | None = None,
                          caps=None, retry: bool = True):
@@ -1113,56 +1049,7 @@ class Engine:
         its output is first given (default: merkle_continue_home's); a hop that reports
         DG_E_CAPACITY is retried, alone with the other such hops, at the sizes it reported
         (retry=False: its element is ("capacity", entries, buckets), the sizes needed)."""
-        self._order()
-        conts = list(conts)
-        k = len(conts)
-        s = tree.store
-        mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
-        t, ss = tree.abi(), s.abi()
-        hops = (_abi.dg_cont_hop * max(k, 1))()
-        cins = [c.abi() for c in conts]
-        sizes, outs, cos, keys = [], [None] * k, [None] * k, []
-        for j, c in enumerate(conts):
-            oc, ob = 4 * max(c.n, 1), max(c.n, 1)
-            if max_entries is not None:
-                oc = min(oc, max(int(max_entries), 1))
-            sizes.append(tuple(caps[j]) if caps is not None and caps[j] is not None else (oc, ob))
-            cap = max(c.n, 1) + s.n
-            keys.append(torch.empty(max(int(cap), 1), dtype=_I64, device=self.device))
-            hops[j].in_ = C.pointer(cins[j])
-            hops[j].keys = keys[j].data_ptr()
-            hops[j].cap = int(cap)
-        todo = list(range(k))
-        res = [None] * k
-        for attempt in range(3):
-            batch = (_abi.dg_cont_hop * max(len(todo), 1))()
-            for i, j in enumerate(todo):
-                outs[j] = MerkleCont.empty(sizes[j][0], sizes[j][1], self.device)
-                cos[j] = outs[j].abi()
-                hops[j].out = C.pointer(cos[j])
-                batch[i] = hops[j]
-            check(self.lib.dg_merkle_continues(self.h, C.byref(t), C.byref(ss), len(todo), batch, levels, mx))
-            again = []
-            for i, j in enumerate(todo):
-                h = batch[i]
-                if h.rc == _abi.DG_E_CAPACITY and not retry:
-                    res[j] = ("capacity", int(cos[j].n), int(cos[j].n_buckets))
-                elif h.rc == _abi.DG_E_CAPACITY and attempt < 2:
-                    sizes[j] = (max(int(cos[j].n), sizes[j][0]), max(int(cos[j].n_buckets), sizes[j][1]))
-                    again.append(j)
-                elif h.rc != _abi.DG_OK:
-                    res[j] = ("error", h.rc)
-                elif h.status == _abi.DG_CONT_DECLINED:
-                    res[j] = ("declined",)
-                elif h.status == 1:
-                    outs[j]._set(cos[j])
-                    res[j] = ("continue", outs[j])
-                else:
-                    res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total))
-            todo = again
-            if not todo:
-                break
-        return res
+        return self._hops(tree, conts, None, levels, max_entries, caps, None, retry)
 
     def merkle_continues_take(self, tree: MerkleTree, conts, want_rows, levels: int = 8,
                               max_entries: int | None = None, caps=None, row_caps=None, retry: bool = True):
@@ -1174,10 +1061,17 @@ class Engine:
         merkle_continues'.  `row_caps`: per hop the rows its Store is first given (default:
         take_keys'); a take that reports DG_E_CAPACITY is retried at the size it reported
         (retry=False: ("ok", keys, total, None, ("capacity", rows needed)))."""
+        return self._hops(tree, conts, want_rows, levels, max_entries, caps, row_caps, retry)
+
+    def _hops(self, tree, conts, want_rows, levels, max_entries, caps, row_caps, retry):
+        """The body of merkle_continues (want_rows None) and merkle_continues_take: the hops'
+        buffers, up to three launches -- each of the hops (and takes) that reported
+        DG_E_CAPACITY in the one before, at the sizes they reported -- and every hop's result."""
         self._order()
         conts = list(conts)
-        want = [bool(w) for w in want_rows]
         k = len(conts)
+        take = want_rows is not None
+        want = [bool(w) for w in want_rows] if take else [False] * k
         assert len(want) == k
         s = tree.store
         mx = (1 << 64) - 1 if max_entries is None else int(max_entries)
@@ -1187,10 +1081,8 @@ class Engine:
         sizes, outs, cos, keys = [], [None] * k, [None] * k, []
         rsize, rows, offs, takes = [0] * k, [None] * k, [None] * k, [None] * k
         for j, c in enumerate(conts):
-            oc, ob = 4 * max(c.n, 1), max(c.n, 1)
-            if max_entries is not None:
-                oc = min(oc, max(int(max_entries), 1))
-            sizes.append(tuple(caps[j]) if caps is not None and caps[j] is not None else (oc, ob))
+            sizes.append(tuple(caps[j]) if caps is not None and caps[j] is not None
+                         else self._cont_sizes(c, max_entries))
             cap = max(c.n, 1) + s.n
             if want[j] and max_entries is not None:
                 cap = min(cap, max(int(max_entries), 1))
@@ -1207,7 +1099,7 @@ class Engine:
         res = [None] * k
         for attempt in range(3):
             batch = (_abi.dg_cont_hop * max(len(todo), 1))()
-            tptr = (C.POINTER(_abi.dg_cont_take) * max(len(todo), 1))()
+            tptr = (C.POINTER(_abi.dg_cont_take) * max(len(todo), 1))() if take else None
             for i, j in enumerate(todo):
                 outs[j] = MerkleCont.empty(sizes[j][0], sizes[j][1], self.device)
                 cos[j] = outs[j].abi()
@@ -1218,8 +1110,11 @@ class Engine:
                     takes[j] = _abi.dg_cont_take(rows=rows[j].abi(), offs=offs[j].data_ptr())
                     takes[j].rows.cap = rsize[j]
                     tptr[i] = C.pointer(takes[j])
-            check(self.lib.dg_merkle_continues_take(self.h, C.byref(t), C.byref(ss), len(todo), batch, tptr,
-                                                    levels, mx))
+            if take:
+                check(self.lib.dg_merkle_continues_take(self.h, C.byref(t), C.byref(ss), len(todo), batch, tptr,
+                                                        levels, mx))
+            else:
+                check(self.lib.dg_merkle_continues(self.h, C.byref(t), C.byref(ss), len(todo), batch, levels, mx))
             again = []
             for i, j in enumerate(todo):
                 h = batch[i]
@@ -1244,7 +1139,7 @@ class Engine:
                     res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total), None, ("capacity", int(takes[j].rows.n)))
                 else:
                     check(takes[j].rc)
-                    rows[j].n = int(takes[j].rows.n)
+                    rows[j]._set(takes[j].rows)
                     res[j] = ("ok", keys[j][: h.n_keys], int(h.n_total), offs[j][: h.n_keys + 1], rows[j])
             todo = again
             if not todo:
@@ -1267,7 +1162,7 @@ class Engine:
             out = Store.empty(max(s.n, 1), self.device)
         si, so = s.abi(), out.abi()
         check(self.lib.dg_sort_store(self.h, C.byref(si), C.byref(so)))
-        out.n = int(so.n)
+        out._set(so)
         return out
 
     def sort_context(self, c: Context, out: Context | None = None) -> Context:
@@ -1277,7 +1172,7 @@ class Engine:
             out = Context.empty(c.kind, max(c.n, 1), self.device)
         ci, co = c.abi(), out.abi()
         check(self.lib.dg_sort_context(self.h, C.byref(ci), C.byref(co)))
-        out.n, out.kind = int(co.n), int(co.kind)
+        out._set(co)
         return out
 
     # ---------------------------------------------------------------- interning
@@ -1305,7 +1200,7 @@ class Engine:
         n = int(ids.numel())
         used = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
         k = len(stores)
-        arr = (_abi.dg_store * max(k, 1))(*[s.abi() for s in stores])
+        arr = self._structs(stores, _abi.dg_store)
         nu, nx = C.c_uint64(0), C.c_uint64(0)
         check(self.lib.dg_mark_ids(self.h, arr, k, int(column), _ptr(ids, _abi.P64), n,
                                    C.c_void_p(used.data_ptr()), C.byref(nu), C.byref(nx)))
