@@ -232,6 +232,9 @@ _SIGS = {
                                C.POINTER(dg_store)]),
     "dg_take_keysets": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.c_int, C.POINTER(C.c_void_p), P64,
                                   P64, P64, P64, C.c_uint64, P64, C.POINTER(dg_store)]),
+    "dg_replace_keysets": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.c_uint64, P64, P64,
+                                     C.POINTER(dg_store), P64, C.POINTER(dg_store), C.c_void_p, P64,
+                                     C.POINTER(C.c_int)]),
     "dg_mutate_batch": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
                                   C.c_uint32, C.c_uint64, C.c_void_p, P64, P64, PI64, P64,
                                   C.c_uint64, C.POINTER(dg_store), C.POINTER(dg_context), P64,

@@ -2,9 +2,12 @@
 lib/delta_crdt/causal_crdt.ex): applying a delta to a replica's state and the diffs
 its `on_diffs` subscriber receives.  The GenServer, neighbours and sync messages are
 out of scope here (tests/binding_mirror.py restates the handlers over the NIF's
-mirror).  The MerkleMap (aw_lww_map.merkle_map, store.MerkleTree), the
-sharded round (sharding.py, §6) and storage (storage.py, §4.6) are in scope and have modules
-of their own.
+mirror).  The MerkleMap (aw_lww_map.merkle_map, store.MerkleTree) and the
+sharded round (sharding.py, §6) are in scope and have modules of their own.  So has storage
+(storage.py): the whole-state snapshot the reference's write_to_storage would write after
+every delta (causal_crdt.ex:238-250), and beside it the per-delta journal
+(§4.18) that the two resident update functions below append to when given one -- the part
+of update_state_with_delta's write_to_storage (:383-404) a resident replica can afford.
 
     from delta_crdt_ex_amd import aw_lww_map as M, causal_crdt as CC
     st = M.compress_dots(M.new())
@@ -96,13 +99,43 @@ def update_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys):
     return new, _callback_diffs(U, order, u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())
 
 
+def _changed_rows_out(n_keys: int, n_delta_rows: int, device) -> Store:
+    """Room for a join's changed keys' rows (dg_join_delta_rows' `rows`): a few per key."""
+    return Store.empty(4 * n_keys + n_delta_rows + 16, device)
+
+
+def _journal_effect(journal, state: M.AWLWWMap, tree, changed, rows, ctx=None):
+    """Append the effect of the delta(s) just joined: `changed` (ascending key ids, numpy) and
+    their joined `rows` -- five numpy columns, or the Store the join filled; where the join
+    reports more rows than the Store holds (rows.n > rows.cap: not written, deltagpu.h) they
+    are taken from the joined state instead -- with the joined context (`ctx` = (node, cnt)
+    when the join brought it home) and the tree's root behind it."""
+    if isinstance(rows, Store):
+        if rows.n > rows.cap:
+            kt = torch.from_numpy(np.ascontiguousarray(changed).view(np.int64).copy()).to(state.rows.device)
+            rows = M.engine().take_keys(state.rows, kt)
+        rows = rows.to_numpy()
+    node, cnt = ctx if ctx is not None else state.ctx.to_numpy()
+    journal.append(journal.sequence_number + 1, changed, rows, (state.ctx.kind, node, cnt),
+                   root=tree.root() if tree is not None else None)
+
+
 def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys, spare: Store,
-                                     tree=None):
+                                     tree=None, journal=None):
     """update_state_with_delta on a state that stays resident: `state` itself becomes the
     join (its rows in place, or through `spare` when a key's row count changed; its context
     the union; `tree`, a MerkleTree over its rows, follows) and the same `diffs` value is
     returned.  Nothing of the old state is kept on the host or read back: the reads before
-    the join come out of the join's own walk of each key (Engine.join_delta_diffs)."""
+    the join come out of the join's own walk of each key (Engine.join_delta_diffs).
+
+    `journal` (a storage.Journal for this replica's base): one record is appended per call --
+    the changed keys and their joined rows, which the join brings home anyway, with the joined
+    context, sequence number journal.sequence_number + 1 and the tree's root (a call that
+    changes no key still records the context).  The journal is for the deltas CausalCrdt
+    makes, whose rows all lie in their keyset: for those the join's `changed` is exact
+    (deltagpu.h, dg_join_delta), and so the record is the whole effect.  A delta with rows
+    outside its keyset changes keys `changed` does not name; the root in the record is what
+    catches that, when storage.read replays the journal and compares."""
     U = state.universe
     order, kt = _keyset(U, keys)
     eng = M.engine()
@@ -116,16 +149,21 @@ def update_resident_state_with_delta(state: M.AWLWWMap, delta: M.AWLWWMap, keys,
     state._host = None
     if home is not None:
         changed, (old_val, new_val, flags) = home[0], home[4]
+        if journal is not None:  # (the home block holds the rows and the context too)
+            _journal_effect(journal, state, tree, changed, home[1], home[2])
     else:
+        out = _changed_rows_out(int(kt.numel()), delta.rows.n, rows.device) if journal is not None else None
         changed, old_val, new_val, flags, _ = eng.join_delta_diffs(rows, ctx, delta.rows, delta.ctx, kt,
-                                                                   spare, tree)
+                                                                   spare, tree, rows=out)
         changed, old_val, new_val, flags = u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy()
+        if journal is not None:
+            _journal_effect(journal, state, tree, changed, out)
     if len(changed) == 0:
         return None
     return _callback_diffs(U, order, changed, old_val, new_val, flags)
 
 
-def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tree=None):
+def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tree=None, journal=None):
     """update_resident_state_with_delta for a batch [(delta, keys), ...] -- the pending
     {:diff, delta, keys} messages of a replica's mailbox -- as ONE call (Engine.join_deltas_keyed, or
     Engine.join_deltas for a batch that declines: the fold, the changed keys, the MerkleMap
@@ -134,10 +172,12 @@ def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tr
     a key is reported once, with its read before the first and after the last delta (a key
     whose read went a -> b -> a reports nothing; the per-delta callbacks the reference would
     have made are not reproduced), in the order of each key's first occurrence over the
-    batch's key lists.  A batch of one delta is the single-delta function."""
+    batch's key lists.  A batch of one delta is the single-delta function.  `journal`: as for
+    the single-delta function, ONE record for the batch -- its net changed keys and their rows
+    after the last delta."""
     batch = list(batch)
     if len(batch) == 1:
-        return update_resident_state_with_delta(state, batch[0][0], batch[0][1], spare, tree)
+        return update_resident_state_with_delta(state, batch[0][0], batch[0][1], spare, tree, journal)
     U = state.universe
     eng = M.engine()
     order, seen, kts = [], set(), []
@@ -159,8 +199,13 @@ def update_resident_state_with_deltas(state: M.AWLWWMap, batch, spare: Store, tr
     # mirror always tries the keyed call: on a state of about a million keys that is slower
     # than the streaming fold alone at every batch size measured, and a batch
     # declined on the device has paid for the attempt before the streaming fold runs.
-    got = eng.join_deltas_keyed(*args)
-    changed, old_val, new_val, flags, _ = got if got is not None else eng.join_deltas(*args)
+    out = None
+    if journal is not None:
+        out = _changed_rows_out(sum(int(kt.numel()) for kt in kts), sum(d.rows.n for d, _ in batch), rows.device)
+    got = eng.join_deltas_keyed(*args, rows=out)
+    changed, old_val, new_val, flags, _ = got if got is not None else eng.join_deltas(*args, rows=out)
+    if journal is not None:
+        _journal_effect(journal, state, tree, u64(changed), out)
     if changed.numel() == 0:
         return None
     return _callback_diffs(U, order, u64(changed), u64(old_val), u64(new_val), flags.cpu().numpy())

@@ -356,7 +356,7 @@ int dg_engine_destroy(dg_engine* e) {
   if (!e) return DG_OK;
   hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
-  for (Buf* b : {&e->state, &e->tmp, &e->counts, &e->fold, &e->spl, &e->ubuf, &e->sml, &e->kdb, &e->kdz,
+  for (Buf* b : {&e->state, &e->tmp, &e->counts, &e->fold, &e->spl, &e->ubuf, &e->sml, &e->kdb, &e->kdz, &e->rpl,
                  &e->diff_bsum})
     if (b->p) hipFree(b->p);
   if (e->d_counts) hipFree(e->d_counts);

@@ -424,4 +424,32 @@ inline KeyedScratch keyed_layout(Arena& a, uint64_t k, size_t seg_bytes, size_t 
   return s;
 }
 
+// dg_replace_keysets (engine rpl; the splice behind it carves engine spl by splice_layout).
+// Per item of the m keys laid end to end: its first row in its record's segment and its rows |
+// per union key (at most m): the key, the winning record's first row and rows, the edit
+// offsets (m + 1: the take's last tile writes entry n_keys) | per union tile its tails and
+// their offset | the sort's scratch
+struct ReplayScratch {
+  uint64_t* item_lo;
+  uint32_t* item_len;
+  uint64_t *ukeys, *u_lo;
+  uint32_t* u_len;
+  uint64_t* e_off;
+  uint64_t *tile_cnt, *tile_off;
+  void* sort_tmp;
+};
+inline ReplayScratch replay_layout(Arena& a, uint64_t m, uint64_t union_tiles, size_t sort_bytes) {
+  ReplayScratch s;
+  s.item_lo = a.take<uint64_t>(m);
+  s.item_len = a.take<uint32_t>(m);
+  s.ukeys = a.take<uint64_t>(m);
+  s.u_lo = a.take<uint64_t>(m);
+  s.u_len = a.take<uint32_t>(m);
+  s.e_off = a.take<uint64_t>(m + 1);
+  s.tile_cnt = a.take<uint64_t>(union_tiles);
+  s.tile_off = a.take<uint64_t>(union_tiles);
+  s.sort_tmp = a.take<char>(sort_bytes);
+  return s;
+}
+
 }  // namespace dg

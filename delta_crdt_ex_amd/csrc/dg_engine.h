@@ -44,6 +44,8 @@ struct dg_engine {
   // dg_join_delta's one-wait path (kdelta.hip): per-key figures, the splice index, the
   // union context (DG_KD=0: the splice path with its host waits, for A/B)
   Buf kdb;
+  Buf rpl;  // dg_replace_keysets' per-item and per-union-key arrays (its own: the tree update
+            //   behind them carves `tmp`, the splice `spl`)
   Buf kdz;  // its tree update's dirty flags and chunk row-count changes: zero between calls
             //   (the re-reduction consumes them)
   bool kd = true;

@@ -180,6 +180,37 @@ hipError_t launch_keysets_union(const u64* cat, const uint8_t* set, const u32* i
                                 u64* ukeys, u64* masks, u64 cap, const Scan& scan, u64* d_count,
                                 hipStream_t st);
 
+// ---- replay.hip (dg_replace_keysets: k journal records -> the union's keys and winning rows)
+constexpr int RP_BLOCK = 256;    // threads of a check / union workgroup
+constexpr int RP_ITEMS = 4;      // sorted items per thread of the union kernel
+constexpr int RP_TILE = RP_BLOCK * RP_ITEMS;  // sorted items per union workgroup
+inline u64 replay_tiles(u64 m) { return (m + RP_TILE - 1) / RP_TILE; }
+constexpr u32 RP_ERR_KEYS = 1u;  // the input-error word: a keyset not strictly ascending,
+constexpr u32 RP_ERR_ROWS = 2u;  //   a row segment not in store order
+struct ReplayArgs {
+  const u64* keys_cat;  // the m keys of the k records' keysets end to end
+  const u64* key_off;   // k + 1: record j's keys are keys_cat[key_off[j], key_off[j + 1])
+  Rows rows;            // the records' rows end to end
+  const u64* row_off;   // k + 1: record j's rows are rows[row_off[j], row_off[j + 1])
+  u64 k, m;
+  u64* item_lo;         // m: the first row >= the item's key in its own record's segment
+  u32* item_len;        // m: the segment's rows of that key
+  u64* d_sum;           // += the item_len of every item (zero on entry)
+  u32* err;             // |= RP_ERR_* (zero on entry)
+};
+// One thread per item and per row: the item's record (a search of key_off), its order against
+// its predecessor in the keyset, and its rows in its record's segment; the row's order against
+// its predecessor in its segment.  No workgroup waits on another.
+hipError_t launch_replay_check(const ReplayArgs& p, hipStream_t st);
+// The union of the m items in sorted order (item i is keys_cat[idx[i]]; idx == nullptr: the
+// identity): the LAST item of a run of equal keys is the last record naming the key, since the
+// sort is stable and positions ascend with the record.  Count per tile, a one-workgroup scan
+// (*d_count = union keys), then the write: ukeys[g] and the winner's u_lo[g], u_len[g].
+// tile_cnt / tile_off: replay_tiles(m) words each.  Three launches, none waiting inside.
+hipError_t launch_replay_union(const u64* keys_cat, const u32* idx, u64 m, const u64* item_lo,
+                               const u32* item_len, u64* tile_cnt, u64* tile_off, u64* ukeys, u64* u_lo,
+                               u32* u_len, u64* d_count, hipStream_t st);
+
 // ---- splice.hip (a sparse keyed join applied to a large state without merging it)
 // The keyed join of a small delta into a large state, as a splice: the state's rows of the
 // keyset K are taken out (launch_take_keys with the per-key index), joined with the delta

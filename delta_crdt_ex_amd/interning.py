@@ -189,6 +189,7 @@ class Universe:
         self._node_hash = []
         self.val_epoch = 0
         self.terms_version = 0
+        self.sweeps = 0          # sweep() calls: until one, keys are only ever appended
         self.remap_hook = None
         self._tracked = weakref.WeakSet()
 
@@ -345,6 +346,7 @@ class Universe:
                 del self._key_term[kid]
                 del self._key_id[hk]
         self.terms_version += 1
+        self.sweeps += 1
         return {"values": (nv, len(self._val_ids)), "keys": (nk, len(self._key_term))}
 
     def track(self, store):

@@ -386,12 +386,14 @@ class Engine:
         """What every resident join does behind the library's call: when the result landed
         in `spare`, the two Store objects exchange their columns (`state` always holds the
         joined rows, `spare` the old ones with n = 0); the counts come back from the structs
-        and `tree` indexes `state`."""
+        and `tree` indexes `state`.  `state_ctx` None: a call that leaves the context alone
+        (replace_keysets)."""
         if swapped:
             state.swap_columns(spare)
             spare.n = 0
         state._set(ss)
-        state_ctx._set(sc)
+        if state_ctx is not None:
+            state_ctx._set(sc)
         if tree is not None:
             tree.n_keys = int(t.n_keys) & ((1 << 64) - 1)
             tree.store = state
@@ -575,6 +577,51 @@ class Engine:
         out._set(so)
         n = int(nu.value)
         return ukeys[:n], masks[:n], offs[:n + 1], out
+
+    def replace_keysets(self, state: Store, keysets, row_stores, spare: Store,
+                        tree: MerkleTree | None = None):
+        """k journal records applied to a resident state in one splice (dg_replace_keysets):
+        for every key of `keysets[j]` (ascending unique device int64) the state's rows become
+        `row_stores[j]`'s rows of that key (none: the key is removed); the last record naming
+        a key wins, every other row stays, `tree` (indexing `state`) follows.  The records are
+        laid end to end here and the offsets computed; the swap is committed as after
+        join_delta.  Returns (number of union keys, swapped)."""
+        self._order()
+        k = len(keysets)
+        if len(row_stores) != k:
+            raise ValueError("replace_keysets: one row store per keyset")
+        key_off = np.zeros(k + 1, np.int64)
+        row_off = np.zeros(k + 1, np.int64)
+        np.cumsum(np.array([int(t.numel()) for t in keysets], np.int64), out=key_off[1:])
+        np.cumsum(np.array([s.n for s in row_stores], np.int64), out=row_off[1:])
+        m, n = int(key_off[k]), int(row_off[k])
+        keys_cat = (torch.cat([t.reshape(-1) for t in keysets]) if m else
+                    torch.zeros(1, dtype=_I64, device=self.device))
+        rows_cat = Store.empty(n, self.device)
+        with_rows = [s for s in row_stores if s.n]
+        for f in ("key", "val", "ts", "node", "cnt"):
+            if with_rows:
+                getattr(rows_cat, f)[:n].copy_(torch.cat([getattr(s, f)[: s.n] for s in with_rows]))
+        rows_cat.n = n
+        return self.replace_keysets_cat(state, keys_cat, key_off, rows_cat, row_off, spare, tree)
+
+    def replace_keysets_cat(self, state: Store, keys_cat: torch.Tensor, key_off, rows_cat: Store, row_off,
+                            spare: Store, tree: MerkleTree | None = None):
+        """replace_keysets on records already laid end to end (what a journal reader has):
+        `keys_cat` (device int64) and `rows_cat` with their k + 1 host offsets each."""
+        k = len(key_off) - 1
+        d_koff = torch.from_numpy(np.ascontiguousarray(key_off, np.int64)).to(self.device)
+        d_roff = torch.from_numpy(np.ascontiguousarray(row_off, np.int64)).to(self.device)
+        self._order()  # (uploads and concatenations ran on torch's stream)
+        ss, sr, sp = state.abi(), rows_cat.abi(), spare.abi()
+        t = tree.abi() if tree is not None else None
+        nu = C.c_uint64(0)
+        sw = C.c_int(0)
+        check(self.lib.dg_replace_keysets(self.h, C.byref(ss), k, _ptr(keys_cat, _abi.P64), _ptr(d_koff, _abi.P64),
+                                          C.byref(sr), _ptr(d_roff, _abi.P64), C.byref(sp), _ref(t), C.byref(nu),
+                                          C.byref(sw)))
+        self._commit_join(state, None, spare, tree, ss, None, t, sw.value)
+        return int(nu.value), bool(sw.value)
 
     def mutate_batch(self, state: Store, ctx: Context, node: int, kind: torch.Tensor,
                      key: torch.Tensor, val: torch.Tensor, ts: torch.Tensor,

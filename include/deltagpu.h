@@ -515,6 +515,38 @@ int dg_take_keysets(dg_engine* e, const dg_store* s, int k, const uint64_t* cons
                     const uint64_t* n_keys, uint64_t* ukeys, uint64_t* masks, uint64_t* offs,
                     uint64_t cap_keys, uint64_t* n_ukeys, dg_store* out);
 
+/* ---- journal replay --------------------------------------------------------- */
+/* k journal records (storage.py: per applied delta its changed keys and those keys' rows
+ * after it) applied to a resident state in ONE splice.  For j = 0 .. k-1 in order and every key
+ * of record j's keyset keys_cat[key_off[j], key_off[j + 1]) (strictly ascending), the state's
+ * rows of that key become record j's rows of that key: the rows with that key in the segment
+ * rows_cat[row_off[j], row_off[j + 1]), which is in store order (the full tuple strictly
+ * ascending); a segment without rows of the key removes the key.  So for every key of the
+ * keysets' union the LAST record naming it decides, every other row of the state is untouched,
+ * and the result is bit-identical to applying the records one after another.  k is not capped:
+ * a record is a position, not a mask bit (k and the keys in all are below 2^32).
+ *   keys_cat, key_off, rows_cat's columns, row_off   device memory; the offsets have k + 1
+ *             entries, start at 0, ascend, and end at the key total and at rows_cat->n.
+ *   spare     as dg_join_delta: spare->cap >= state->n + rows_cat->n (DG_E_CAPACITY).
+ *   *swapped  0 when every union key keeps its row count: the state was written in place and
+ *             `spare` was not touched; else 1: the new state was written to `spare` and the two
+ *             dg_store structs were exchanged.
+ *   tree      (optional) indexes `state`; afterwards it equals dg_merkle_build of the new state
+ *             node for node, bucket counts and n_keys included.
+ *   *n_union  the keys of the union.
+ * The context is the caller's matter (a restore uploads the last record's).  All or nothing:
+ * state, spare and tree are untouched when a keyset is not strictly ascending or a row segment
+ * is not in store order (DG_E_ORDER), a row's key is not in its own record's keyset (found on
+ * the device: the rows of every (record, key) must add up to rows_cat->n; DG_E_INVAL), a key
+ * lies outside the tree's shard (DG_E_INVAL), a bucket would hold more than 65535 rows or
+ * `spare` is too small (DG_E_CAPACITY).  State and spare columns are 16-byte aligned as
+ * dg_store_alloc makes them (DG_E_INVAL).  k == 0 or an empty union: DG_OK, nothing done.
+ * A start-up path: synchronous, with a host wait per step (the offsets, the checks, the
+ * union's size, the takes and the index, the tree, the copy). */
+int dg_replace_keysets(dg_engine* e, dg_store* state, uint64_t k, const uint64_t* keys_cat,
+                       const uint64_t* key_off, const dg_store* rows_cat, const uint64_t* row_off,
+                       dg_store* spare, dg_merkle* tree, uint64_t* n_union, int* swapped);
+
 /* ---- batched mutations ----------------------------------------------------- */
 /* A batch of AWLWWMap.add/4 and remove/3 operations by node `node` as ONE delta
  * (aw_lww_map.ex:99-146; CausalCrdt applies each op's delta with keys = [key] as the op
