@@ -4,8 +4,8 @@
 // running back to back).
 //
 // One workgroup of NT threads covers NT / KD_BLOCK of kd_count_kernel's tiles, one key per
-// thread: the key's new rows in tuple order -- in place when no key's row count changed
-// (and only for changed keys), else straight to their final places in the spare store --
+// thread: the key's new rows in tuple order -- in place when the count kernel set KD_MOVED for
+// no key (and only for changed keys), else straight to their final places in the spare store --
 // the changed keys and their rows, the splice index of the rows that move (splice.hip),
 // and (workgroup 0) the union context into the state's.  Every state write is skipped when
 // the tree update reported an input error (all or nothing).
@@ -119,6 +119,10 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
     }
   }
   // the key's new rows in tuple order: the kept state rows and the new delta rows (disjoint)
+  // (In place, slot a_lo + o is stored before the next kept state row a_lo + i is loaded, so
+  // o must never pass i: the count kernels set KD_MOVED for a key where it would -- new rows
+  // ahead of two kept rows that a removed row makes room for -- and such a call is written to
+  // the spare store instead.)
   const bool wr_state = !tree_bad;  // in place: only when the tree took the update
   const bool wr_rows = chg && p.has_rows && r_off + ne <= p.rows_cap;
   if (!(wr_state || moved) && !wr_rows && !chg) return;

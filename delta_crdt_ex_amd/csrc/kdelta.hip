@@ -23,7 +23,8 @@
 //                     kd_count_diffs_kernel (dg_join_delta_diffs) is the same walk that also
 //                     keeps read/1's winner of the key's rows before and after the join.
 //   kd_finish_kernel  (merkle_build.hip + dg_kdw.h, one launch) one thread per key: its new rows --
-//                     in place when no key's row count changed, else straight to their
+//                     in place when no key's row count changed (and no key's in-place
+//                     write would read back a row it wrote: KD_MOVED), else straight to their
 //                     final places in the spare store -- the changed keys and their rows
 //                     (device or page-locked host memory), the splice index of the rows
 //                     that move (splice.hip), the union context into the state's; every
@@ -205,7 +206,8 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
   u64 v[KD_NV] = {0, 0, 0, 0, 0, 0, 0};
   u64 a_lo = 0, d_lo = 0, am = 0, dm = 0, dh = 0;
   u32 na = 0, nd = 0, ne = 0;
-  bool chg = false, big = false;
+  bool chg = false, big = false, back = false;
+  u32 wo = 0;  // rows the write (dg_kdw.h) has stored when it loads the next kept state row
   u64 k = 0;
   u64 ov = 0, nv = 0;    // (DIFFS) the old and the new winner's value id (no row: 0) ...
   i64 ots = 0, nts = 0;  // ... and ts
@@ -269,8 +271,10 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
           nv = wn ? ra.val : nv;
         }
         if (keep) {
+          back |= wo > i;  // written in place, slot i would hold an output row by then
           am |= 1ull << i;
           ne++;
+          wo = ne;
         } else {
           chg = true;
           if (p.has_tree && DG_KD_EXP == 0) dh -= rh_row(p.t.th, ra);
@@ -320,7 +324,16 @@ __device__ __forceinline__ void kd_count_body(const KdArgs& p) {
   v[3] = chg ? ne : 0;
   v[4] = nd;
   v[5] = (u64)(i64)((int)(ne > 0) - (int)(na > 0));
-  v[6] = (big ? KD_BIG : 0u) | (ne != na ? KD_MOVED : 0u);
+  // rows move (the write goes through the spare store, not in place) when the key's row count
+  // changes, and also when the in-place write would read back a row it has just written:
+  // dg_kdw.h stores output row o at slot o, and loads kept state row i right after it has
+  // stored the kept row before it -- by then it has stored `wo` rows, every kept row and every
+  // new row up to there, and wo > i means slot i is gone ([X, Y, Z] -> [D, X, Y] came out
+  // [D, X, X]).  A new row behind the kept rows, or before the only kept row, is no hazard
+  // and stays in place.  (kk_count_body below flags every key of several rows that loses one
+  // and gains one: wider, and as safe.)
+  const bool moved = ne != na || back;
+  v[6] = (big ? KD_BIG : 0u) | (moved ? KD_MOVED : 0u);
 #pragma unroll
   for (int q = 0; q < KD_NV; q++) {
     u64 x = v[q];

@@ -3,13 +3,7 @@
 dg_join_delta_home_diffs or dg_join_delta_diffs): the diffs list every call returns equals
 diffs_to_callback/3's rule (causal_crdt.ex:361-381) applied to the term oracle's reads
 before and after -- and a replica that uses ONLY those lists, reading no old struct,
-delivers the `received` streams of CPU-only replicas.
-
-The large path and the known in-place defect.  ADVICE.md describes dg_kdw.h's in-place write
-of a multi-row key reading back a row it just wrote when NO key of the call changes its row
-count; that is another change's fix.  Every call here that takes the large path (more than
-512 keys) therefore adds at least one key the state lacks, so rows move and that write is
-not reached: a failure here is this feature's.  The small path is not affected."""
+delivers the `received` streams of CPU-only replicas."""
 import pytest
 from hypothesis import HealthCheck, given, settings
 
@@ -111,9 +105,10 @@ def _peer(nodes, keys, value_of, ts0):
 
 
 def test_history_of_diffs_calls():
-    """One-key ops, a 600-key batch and a 2,000-key sync delta of three entries per key (the
-    large path; its changed rows overflow the return block: grow and re-take), then small
-    calls again on the same engine; values include nil, 1 and 1.0, tuples."""
+    """One-key ops, a 600-key batch, 600 overwrites that add no key (the large path in place)
+    and a 2,000-key sync delta of three entries per key (the large path with moves; its changed
+    rows overflow the return block: grow and re-take), then small calls again on the same
+    engine; values include nil, 1 and 1.0, tuples."""
     r = Resident()
     ts = iter(range(1000, 10 ** 9))
     vals = [None, 1, 1.0, (1, 2), "x", b"y", True]
@@ -142,6 +137,13 @@ def test_history_of_diffs_calls():
     assert len({op[1] for op in ops}) == 604
     d = r.mutate(1, ops)
     assert len(d) > 400
+    # 600 overwrites of keys that are all there, one entry each: no key is added and no row
+    # count changes, so the large path writes in place; every key reads another value
+    ops = [("add", 100 + i, vals[(i + 1) % len(vals)], next(ts)) for i in range(560)]
+    ops += [("add", i, "z", next(ts)) for i in range(0, 8, 2)] + [("add", 1000 + i, i, next(ts)) for i in range(36)]
+    assert len({op[1] for op in ops}) == 600 and all(len(r.terms.value[tg(op[1])]) == 1 for op in ops)
+    d = r.mutate(1, ops)
+    assert len(d) == 600
     # a sync delta of 2,000 keys, three concurrent entries per key, 560 of them known here
     keys = list(range(100, 2100))
     peer = _peer([2, 3, 4], keys, lambda j, i: (j, i) if i % 3 else float(i), 500)
