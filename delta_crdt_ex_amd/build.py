@@ -25,7 +25,7 @@ _SUFFIX = ("_stamps" if STAMPS else "") + (("_" + VARIANT.replace("=", "").repla
 OBJ = os.path.join(HERE, "_build" + _SUFFIX)
 LIB = os.path.join(HERE, "ab", "libdeltagpu" + _SUFFIX + ".so") if _SUFFIX else os.path.join(HERE, "libdeltagpu.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-SOURCES = ["join.hip", "join_stream.hip", "join_twopass.hip", "join_changes.hip", "kfold.hip", "take.hip", "takesets.hip", "replay.hip", "splice.hip", "small.hip", "kdelta.hip", "mutate.hip", "segred.hip",
+SOURCES = ["join.hip", "join_stream.hip", "join_twopass.hip", "join_changes.hip", "kfold.hip", "take.hip", "takesets.hip", "replay.hip", "splice.hip", "small.hip", "kdelta.hip", "kkeyed.hip", "mutate.hip", "segred.hip",
            "merkle_build.hip", "merkle_diff.hip", "merkle_cont.hip", "remap.hip", "mark.hip", "sort.hip", "sdiff.hip",
            "api_engine.hip", "api_join.hip", "api_join_delta.hip", "api_fold.hip", "api_join_deltas.hip", "api_merkle.hip", "api_ops.hip", "api_takesets.hip", "api_replay.hip"]
 ARCH = os.environ.get("DG_OFFLOAD_ARCH", "gfx950")

@@ -3,7 +3,7 @@
 // CausalCrdt.update_state_with_delta needs from it -- the fold (api_fold.hip), the diff of
 // the state before and after, the tree step, the context and the exchange of the stores.
 // dg_join_deltas_keyed is the same batch at the cost of the keys it names, for small keyed
-// deltas: the keysets' union, then dg_join_delta's one-wait path over it (kdelta.hip).
+// deltas: the keysets' union, then dg_join_delta's one-wait path over it (kdelta.hip, kkeyed.hip).
 //
 // The changed keys are the batch's NET change: every key whose row set differs between the
 // state before and after.  For sync- and mutation-shaped deltas (every delta row's key is in
@@ -219,7 +219,7 @@ int dg_join_deltas(dg_engine* e, dg_store* state, dg_context* state_ctx, int k, 
   return DG_OK;
 }
 
-// The same batch at the cost of the keys it names (kdelta.hip kk_count_kernel): the keysets'
+// The same batch at the cost of the keys it names (kkeyed.hip kk_count_kernel): the keysets'
 // union with its masks as dg_take_keysets builds it (two waits: the keysets' order, the union's
 // size), then dg_join_delta's one-wait path with the fold's count kernel in the place of the
 // join's -- the VV tables, the count (each union key's candidates folded, its new rows into

@@ -294,6 +294,29 @@ __device__ __forceinline__ u64 interp_lower_bound(const u64* k, u64 lo, u64 hi, 
   return l2;
 }
 
+// The first row of key x in key[0, n) (its lower bound) and the key's run, counted until it is
+// past LIMIT: 4 rows a round trip, the four loads unconditional at clamped indices so that
+// they are issued together.  (lo == n -- x sorts after every row, or n == 0 -- loads nothing.)
+template <u32 LIMIT>
+__device__ __forceinline__ void key_run(const u64* key, u64 n, u64 x, u64& lo, u32& run) {
+  lo = interp_lower_bound(key, 0, n, x);
+  u64 e = lo;
+  while (e < n) {
+    u64 kk[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const u64 v = key[e + q < n ? e + q : lo];
+      kk[q] = e + q < n ? v : x + 1;
+    }
+    u32 c = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) c += (c == (u32)q && kk[q] == x) ? 1u : 0u;
+    e += c;
+    if (c < 4 || e - lo > LIMIT) break;
+  }
+  run = (u32)(e - lo);
+}
+
 __device__ __forceinline__ bool keyset_has(const u64* keys, u64 n, u64 k) {
   u64 lo = 0, hi = n;
   while (lo < hi) {

@@ -1,7 +1,7 @@
-// dg_kdw.h — the write step of dg_join_delta's one-wait path (kdelta.hip), as a block
+// dg_kdw.h — the write step of dg_join_delta's one-wait path (kdelta.hip; kkeyed.hip), as a block
 // body: merkle_build.hip's kd_finish_kernel runs it in the same launch as the tree's chunk
 // re-reduction (the two read only what kd_count_kernel wrote, so they overlap instead of
-// running back to back).
+// running back to back).  (kd_count_kernel below: or kk_count_kernel, which leaves the same.)
 //
 // One workgroup of NT threads covers NT / KD_BLOCK of kd_count_kernel's tiles, one key per
 // thread: the key's new rows in tuple order -- in place when the count kernel set KD_MOVED for
@@ -43,15 +43,14 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
       }
     }
   }
-  u64 rn = 0;
   u32 na = 0, nd = 0, ne = 0;
   bool chg = false;
   if (u < p.nk) {
-    rn = p.runs[u];
-    na = (u32)(rn & 0xFFFF);
-    nd = (u32)((rn >> 16) & 0xFFFF);
-    ne = (u32)((rn >> 32) & 0xFFFF);
-    chg = (rn >> 48) & 1;
+    const u64 rn = p.runs[u];
+    na = kd_run_na(rn);
+    nd = kd_run_nd(rn);
+    ne = kd_run_ne(rn);
+    chg = kd_run_chg(rn);
   }
   // exclusive in-tile prefixes of (na, ne, chg, chg rows) + the tile's offsets
   const u64 x[4] = {na, ne, chg ? 1u : 0u, chg ? ne : 0u};
@@ -109,7 +108,7 @@ __device__ __forceinline__ void kd_write_block(const KdArgs& p, u64 blk) {
   if (moved) {
     p.end[u] = a_lo + na;
     p.shift[u] = (i64)e_off - (i64)a_off;
-    const u64 end_lo = u > 0 ? p.a_lo[u - 1] + (p.runs[u - 1] & 0xFFFF) : 0ull;
+    const u64 end_lo = u > 0 ? p.a_lo[u - 1] + kd_run_na(p.runs[u - 1]) : 0ull;
     const u64 end_hi = a_lo + na;
     for (u64 t = (end_lo + SPLICE_TILE - 1) / SPLICE_TILE; t <= p.a_tiles && t * SPLICE_TILE < end_hi; t++)
       p.tile_u0[t] = u;

@@ -404,8 +404,8 @@ hipError_t launch_merkle_build(const Rows& s, const MerkleT& t, u64* d_keys, u32
 hipError_t launch_merkle_update(const MerkleT& t, const Rows& olds, const Rows& news, const u64* keys,
                                 u64 n_keys, u32* dirty, u64* d_keys, u32* arrive, u64* hand, i64* cdelta,
                                 u32* err, hipStream_t st);
-// the same from kdelta.hip's per-key figures (runs, dh; skipped when guard && *guard);
-// sign -1 undoes what kdelta.hip's count kernel applied, bit for bit, then the dirty chunks
+// the same from the count kernels' per-key figures (kdelta.hip, kkeyed.hip: runs, dh; skipped when
+// guard && *guard); sign -1 undoes what the count kernel applied, bit for bit, then the dirty chunks
 // are re-reduced
 hipError_t launch_kd_tree(const MerkleT& t, const u64* keys, const u64* runs, const u64* dh, u64 nk,
                           const u64* guard, int sign, u32* dirty, u32* arrive, u64* hand, i64* cdelta,
@@ -420,7 +420,7 @@ constexpr int KD_NV = 7;       // per-workgroup figures: rows, kept rows, change
 constexpr u64 KD_BAD = 1, KD_BIG = 2, KD_CAP = 4;
 constexpr u64 KD_MOVED = 8;    // (flags only) a key's row count changed
 // the count block d_counts[0..8) of this path (and its host mirror): written by the count
-// kernel's last workgroup (kdelta.hip), but KC_CTX; read by the write (dg_kdw.h),
+// kernel's last workgroup (kd_count_tail, dg_kdcount.h), but KC_CTX; read by the write (dg_kdw.h),
 // kd_finish_kernel and the host (api_join_delta.hip)
 enum KdCount {
   KC_EDIT = 0,      // the keyset's joined rows
@@ -446,8 +446,8 @@ struct KdArgs {
   Ctx cd;              // its context, sorted
   const u64* keys;     // the keyset, ascending unique
   u64 nk;
-  // per key (nk): first state row, first delta row, runs (na | nd << 16 | ne << 32 | chg << 48),
-  // kept-row masks, leaf change
+  // per key (nk): first state row, first delta row, runs (kd_run_pack / kd_run_* below), kept-row
+  // masks, leaf change
   u64 *a_lo, *d_lo, *runs, *amask, *dmask, *dh;
   u64* part;           // per count workgroup its KD_NV figures (the write sums the earlier ones)
   u64 ntiles;
@@ -481,12 +481,23 @@ struct KdArgs {
   uint8_t* dflags;
 };
 constexpr u32 KD_DIFF_OLD = 1, KD_DIFF_NEW = 2;  // (deltagpu.h DG_DIFF_OLD / DG_DIFF_NEW)
+// A key's word of KdArgs::runs: its state rows na, its delta (or edit) rows nd and its joined
+// rows ne, 16 bits each (all <= 2 KD_RUN), and whether the key changed.  Written by the count
+// kernels -- 0 for a key over KD_RUN, so nothing reads a change from it -- read by the write
+// (dg_kdw.h) and the tree's undo (merkle_build.hip kd_tree_kernel).
+__host__ __device__ inline u64 kd_run_pack(u32 na, u32 nd, u32 ne, bool chg) {
+  return na | ((u64)nd << 16) | ((u64)ne << 32) | (chg ? 1ull << 48 : 0ull);
+}
+__host__ __device__ inline u32 kd_run_na(u64 rn) { return (u32)(rn & 0xFFFF); }
+__host__ __device__ inline u32 kd_run_nd(u64 rn) { return (u32)((rn >> 16) & 0xFFFF); }
+__host__ __device__ inline u32 kd_run_ne(u64 rn) { return (u32)((rn >> 32) & 0xFFFF); }
+__host__ __device__ inline bool kd_run_chg(u64 rn) { return (rn >> 48) & 1; }
 // kd_count_kernel / kd_count_diffs_kernel (its last workgroup scans)
 hipError_t launch_kd_join(const KdArgs& p, hipStream_t st);
 // kd_finish_kernel (merkle_build.hip): the write (dg_kdw.h) and, with a tree, its dirty chunks' re-reduction in one launch
 hipError_t launch_kd_finish(const KdArgs& p, const u32* dirty, u32* arrive, u64* hand, const i64* cdelta,
                             hipStream_t st);
-// dg_join_deltas_keyed: the fold of k keyed deltas (kfold.hip's rule per candidate tuple) as a
+// kkeyed.hip -- dg_join_deltas_keyed: the fold of k keyed deltas (kfold.hip's rule per candidate tuple) as a
 // thread per key of the keysets' union.  kk_prep_kernel builds kfold_prep's VV tables and C_k;
 // kk_count_kernel is kd_count_kernel's counterpart: it writes each key's surviving NEW rows
 // into the edit store `e` and fills kd's per-key arrays with d = e, so that kd_finish_kernel

@@ -1,6 +1,6 @@
 // dg_tree.h — the device side of the Merkle tree (dg_merkle, include/deltagpu.h): what
 // the tree kernels (merkle_build.hip, merkle_diff.hip, merkle_cont.hip), the keyed delta
-// join (kdelta.hip) and the fused small-delta join (small.hip) share.
+// join (kdelta.hip, kkeyed.hip) and the fused small-delta join (small.hip) share.
 //
 // Tree (MerkleT, dg_launch.h): the keys whose top `sb` bits equal `shard` (a key-hash shard,
 // SURVEY §8(e); sb = 0 covers every key) in 2^depth buckets by the next `depth` bits.

@@ -14,7 +14,8 @@
 //  * update: one thread per changed key re-hashes the key's rows in the old and the
 //    new store and adds the difference to its bucket (put/delete); the upsweep then
 //    re-reduces only the 2^11-bucket chunks an update touched (update_hashes).
-//    kd_tree_kernel is the same put/delete from kdelta.hip's per-key figures.
+//    kd_tree_kernel is the same put/delete from the count kernels' per-key figures (kdelta.hip,
+//    kkeyed.hip; tree_put, dg_kdcount.h).
 //  * kd_finish_kernel: the write of dg_join_delta's one-wait path (dg_kdw.h) and the dirty
 //    chunks' re-reduction by persistent workgroups, in one launch.
 #include "dg_kdw.h"
@@ -556,8 +557,9 @@ __global__ __launch_bounds__(UB) void merkle_update_kernel(MerkleT t, Rows olds,
   if (__ballot(over) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr(err, ERR_COUNT);
 }
 
-// The same put/delete from kdelta.hip's per-key figures: key u changed (runs bit 48) with
-// leaf change dh[u] and row-count change ne - na; sign -1 undoes sign +1.  The distinct-key
+// The same put/delete from the count kernels' per-key figures (tree_put, dg_kdcount.h): key u
+// changed (kd_run_chg of its runs word, dg_launch.h) with leaf change dh[u] and row-count
+// change ne - na; sign -1 undoes sign +1.  The distinct-key
 // change is the count kernel's (d_counts[KC_DKEYS]).  The keys are ascending: segmented sums
 // over the lanes (seg_incl, dg_tree.h) leave ONE atomic per bucket and per chunk.
 __global__ __launch_bounds__(UB) void kd_tree_kernel(MerkleT t, const u64* keys, const u64* runs, const u64* dh,
@@ -572,10 +574,10 @@ __global__ __launch_bounds__(UB) void kd_tree_kernel(MerkleT t, const u64* keys,
   int dr = 0, act = 0;
   if (i < nk) {
     const u64 rn = runs[i];
-    const int na = (int)(rn & 0xFFFF), ne = (int)((rn >> 32) & 0xFFFF);
+    const int na = (int)kd_run_na(rn), ne = (int)kd_run_ne(rn);
     const u64 x = keys[i];
     b = bucket_of(t, x);
-    if (((rn >> 48) & 1)) {
+    if (kd_run_chg(rn)) {
       const u64 dd = sign > 0 ? dh[i] : (u64)0 - dh[i];
       const int r = sign > 0 ? ne - na : na - ne;
       if (dd != 0 || r != 0) {

@@ -509,24 +509,12 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     }
   } else if ((u32)tid < nk) {
     const u64 k = p.keys[tid];
-    const u64 lo = interp_lower_bound(p.a.key, 0, p.a.n, k);
-    u64 e = lo;
-    while (p.a.n > 0) {  // the key's run, 4 rows per round trip (an empty state: none)
-      u64 kk[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {  // (unconditional loads at clamped indices: issued together)
-        const u64 v = p.a.key[e + q < p.a.n ? e + q : lo];
-        kk[q] = e + q < p.a.n ? v : k + 1;
-      }
-      u32 c = 0;
-#pragma unroll
-      for (int q = 0; q < 4; q++) c += (c == (u32)q && kk[q] == k) ? 1u : 0u;
-      e += c;
-      if (c < 4 || e - lo > SA) break;
-    }
+    u64 lo;
+    u32 run;
+    key_run<SA>(p.a.key, p.a.n, k, lo, run);  // (dg_device.h: 4 rows per round trip)
     s.key[tid] = k;
     s.alo[tid] = lo;
-    s.na[tid] = (u32)(e - lo);
+    s.na[tid] = run;
   }
   if (fl) atomicOr(&s.flags, fl);
   __syncthreads();

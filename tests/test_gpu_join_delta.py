@@ -487,6 +487,32 @@ def test_home_from_an_empty_state(engine, with_tree):
             assert np.array_equal(tree.bucket_counts(), fresh.bucket_counts())
 
 
+def test_home_keys_past_the_last_state_row(engine):
+    """Twelve keys -- more than the small kernel has waves, so a thread searches each key
+    (key_run, dg_device.h) and wave_find does not run -- two of them sorting after every state
+    row: one the delta adds, one it only names.  The state is 300 rows in a store exactly that
+    long (Store.from_numpy), so those two searches end at lo == n, where there is no row."""
+    rng = np.random.default_rng(78)
+    n = 300
+    keys = np.unique(rng.integers(0, 1 << 62, n + 20, dtype=np.uint64))[:n]
+    a = {"rows": (keys, np.arange(n, dtype=np.uint64) + 100, np.full(n, 5, np.int64), np.zeros(n, np.uint32),
+                  np.arange(1, n + 1, dtype=np.uint64)),
+         "ctx": (R.VV, np.array([0], np.uint32), np.array([n], np.uint64))}
+    assert state_of(a)[0].cap == n
+    added, named = (1 << 63) + 5, (1 << 63) + 9
+    dk = np.concatenate([keys[::30], np.array([added, named], np.uint64)])
+    assert len(dk) == 12 and dk[-3] == keys[270] < keys[-1] < added < named
+    rk = np.concatenate([keys[::60], np.array([added], np.uint64)])  # five updates and the new key
+    d = {"rows": (rk, np.arange(len(rk), dtype=np.uint64) + 10 ** 6, np.full(len(rk), 9, np.int64),
+                  np.full(len(rk), 1, np.uint32), np.arange(1, len(rk) + 1, dtype=np.uint64)),
+         # (covers the state's dots up to 150: the named keys below row 150 lose their row)
+         "ctx": (R.VV, np.array([0, 1], np.uint32), np.array([n // 2, len(rk)], np.uint64))}
+    _, _, swapped, wr = apply(engine, a, d, dk, depth=8, home=True)
+    assert swapped  # (the new key, the removed rows)
+    assert (wr[0] == np.uint64(added)).sum() == 1 and not (wr[0] == np.uint64(named)).any()
+    assert len(wr[0]) == n - 5 + 6  # rows 0, 30, 60, 90, 120 go; the delta's six rows come in
+
+
 # ---------------------------------------------------------------- wave_find (ADVICE r5)
 # The small path's per-key search (small.hip wave_find): its first row and run, against
 # np.searchsorted, at the sizes where the 64-ary narrowing ends on a window edge (every n in

@@ -152,6 +152,27 @@ def test_ten_count_workgroups(engine):
     assert len(want) > 256
 
 
+def test_count_workgroups_past_one_round(engine):
+    """A state of about 70,000 keys and 64 deltas of 1,025 disjoint keys: 65,600 union keys, 257
+    count workgroups -- the fewest for which the last workgroup's sum over the workgroups'
+    figures (256 per round) takes a second round."""
+    st, _ = random_fold(15, n_keys=90_000, k=0)
+    keys = np.unique(st["rows"][0])
+    assert 65_600 < len(keys) < 75_000
+    _, pool = random_fold(16, n_keys=90_000, k=1, p_keys=1.0, p_outside=0.0)  # rows of every key to draw from
+    prow = pool[0]["rows"]
+    rng = np.random.default_rng(17)
+    pick = rng.permutation(keys)[:65_600].reshape(64, 1025)
+    ds = []
+    for i in range(64):
+        ki = np.sort(pick[i])
+        m = np.isin(prow[0], ki)
+        ds.append({"rows": tuple(c[m] for c in prow), "ctx": pool[0]["ctx"], "keys": ki})
+    assert len(np.unique(np.concatenate([d["keys"] for d in ds]))) == 65_600 == 256 * 256 + 64
+    want, _ = run(engine, st, ds, depth=14)
+    assert len(want) > 10_000
+
+
 def test_union_through_the_sort(engine):
     """64 keysets of about 600 keys: 38,000 items, past the total at which the union ranks the
     items in the keysets (items x keysets <= 2^21) and so through the radix sort."""
