@@ -287,6 +287,8 @@ int dg_engine_create(int device, void* hip_stream, dg_engine** out) {
   {
     const char* v = getenv("DG_JOIN_WORKERS");
     if (v && atoi(v) > 0) e->join_workers = atoi(v);
+    const char* sg = getenv("DG_JOIN_STAGGER");
+    if (sg && atoi(sg) > 0) e->join_stagger = atoi(sg) < 4096 ? atoi(sg) : 4096;
     const char* m = getenv("DG_JOIN_MODE");
     if (m && m[0] == '2') e->join_mode = JOIN_TWO_PASS;
     const char* sp = getenv("DG_SPLICE");

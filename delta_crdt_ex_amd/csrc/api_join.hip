@@ -46,7 +46,8 @@ int join2_enqueue(dg_engine* e, const dg_store* a, const dg_context* ca, const d
   }
   HIP_TRY(launch_join2(rows_of(a), ctx_of(ca), rows_of(b), ctx_of(cb), keys, keys ? n_keys : 0,
                        rows_out_of(out), out_ctx->node, out_ctx->cnt, js.ctx, js.pass,
-                       two_pass ? JOIN_TWO_PASS : JOIN_SINGLE_PASS, sc, e->join_workers, d_counts, st, js.chg));
+                       two_pass ? JOIN_TWO_PASS : JOIN_SINGLE_PASS, sc, e->join_workers, d_counts, st, js.chg,
+                       e->join_stagger));
   if (ps) {
     HIP_TRY(hipEventRecord(e->ev_out, ps));
     HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_out, 0));

@@ -70,6 +70,7 @@ struct dg_engine {
   Buf tmp;                // general scratch
   int join_mode = JOIN_SINGLE_PASS;  // DG_JOIN_MODE=2: two-pass count/compact variant
   int join_workers = 0;           // persistent pass-1 workgroups (0: all resident ones)
+  int join_stagger = 0;           // DG_JOIN_STAGGER: the stream kernel's upper-half delay (0: none)
   // dg_apply_deltas: 0 one pass per <= 64 deltas, delta by delta where an input needs it;
   // DG_APPLY_MODE=fold: always delta by delta; =onepass: never (DG_E_INVAL instead)
   int apply_mode = 0;

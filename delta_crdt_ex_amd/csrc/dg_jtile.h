@@ -59,8 +59,8 @@ struct JoinArgs {
   u32* chg_wu;            // CHG: events after the tile's first that differ from their predecessor
   u64* chg_fk;            // CHG: the tile's first and last event (tiles with events)
   u64* chg_lk;
-  int fused;              // read by no kernel (the fused launch is a kernel of its own, LATE); it
-                          // stays: without it the offsets behind it move and four kernels grow
+  int stagger;            // DG_JOIN_STAGGER (0: none): the stream kernel's workgroups of the upper
+                          // half of a stripe sleep this long before their first tile (STAGGER_SLEEP)
   CtxUnionArgs cu;
 };
 

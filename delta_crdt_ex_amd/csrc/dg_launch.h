@@ -58,7 +58,7 @@ hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& 
                         const u64* keys, u64 n_keys, const RowsOut& out, u32* out_ctx_node,
                         u64* out_ctx_cnt, void* ctx_tmp, void* pass_tmp, int mode,
                         const Scan& scan, int workers, u64* d_counts, hipStream_t st,
-                        void* chg_tmp = nullptr);
+                        void* chg_tmp = nullptr, int stagger = 0);
 // Changed keys (dg_join2_changes): with chg_tmp (chg_layout at join2_tiles) the join
 // records per-tile change events (always the single-pass kernel); launch_join2_changes
 // then drops repeats and compacts them into out[0, cap) (*d_count = changed keys).

@@ -85,7 +85,7 @@ hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& 
                         const u64* keys, u64 n_keys, const RowsOut& out, u32* out_ctx_node,
                         u64* out_ctx_cnt, void* ctx_tmp, void* pass_tmp, int mode,
                         const Scan& scan, int workers, u64* d_counts, hipStream_t st,
-                        void* chg_tmp) {
+                        void* chg_tmp, int stagger) {
   JoinArgs p;
   p.a = a;
   p.b = b;
@@ -134,7 +134,7 @@ hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& 
   // two version vectors: LDS VV tables; a key list: per-tile keyset slices
   const bool fast = ca.kind == 0 && cb.kind == 0;
   const bool keyed = keys != nullptr;
-  p.fused = 0;
+  p.stagger = stagger;
   p.cu = cu;
   const StreamKernels sk = stream_kernels(fast, keyed, chg_tmp != nullptr);
   auto kern = sk.part;
@@ -156,7 +156,6 @@ hipError_t launch_join2(const Rows& a, const Ctx& ca, const Rows& b, const Ctx& 
     if (!no_fuse && gr >= 2 && p.ntiles <= (u64)FUSE_IT * gt) {
       if (!chg_tmp) balance_tiles(p, gt);
       place_splits();
-      p.fused = 1;
       return launch_stream(kern_late, gt + 1, p, st);
     }
   }

@@ -4,16 +4,17 @@
 // prefetched into registers to one of two LDS buffers, issues the loads of its next tile,
 // merges JI positions per thread from LDS (keep/drop: dg_jtile.h), block-scans the keep
 // flags into a u16 compaction list and publishes the tile's count as an {epoch, count}
-// granule in a per-stripe array.  The tile is written out one iteration LATER: by then
-// every workgroup has published its count for that stripe, so each workgroup sums the G
-// counts of the stripe itself (a 1-4 KB coalesced read) instead of chaining look-backs, and
-// the output offset is a running sum over stripes.  Inputs are read once, outputs written
+// granule in a per-stripe array.  The tile is written out one iteration LATER: by then the
+// G tiles before it have (nearly always) published their counts, so each workgroup sums
+// those G counts itself (a 1-4 KB coalesced read) instead of chaining look-backs, and adds
+// them to the offset of its previous tile (dg_jstripe.h).  Inputs are read once, outputs written
 // once: 36 B x (N_in + N_out) of HBM traffic plus the splits' probes (dg_jsplit.h: from
 // the partition launch, or searched by the kernel itself when launched fused, LATE).
 // Here too: the grid's residency check, the 16 instantiations and their launch.
 #include <mutex>
 
 #include "dg_jsplit.h"
+#include "dg_jstripe.h"
 #include "dg_jtile.h"
 
 namespace dg {
@@ -32,9 +33,24 @@ __device__ u64 g_join_stamps[65536 * 16];
         __builtin_amdgcn_s_memrealtime();                                            \
     __builtin_amdgcn_sched_barrier(0);                                               \
   } while (0)
+// Slots 10 and 11 of a workgroup's first tile: where the hardware placed it (XCC_ID in
+// the high word, HW_ID -- CU, SH, SE -- in the low one) and 1 + its blockIdx, so
+// tools/stamps_report.py can say which workgroups share a CU.
+#define JSTAMP_PLACE(tile)                                                                 \
+  do {                                                                                     \
+    if (threadIdx.x == 0 && (tile) < 65536) {                                              \
+      g_join_stamps[(tile) * 16 + 10] =                                                    \
+          ((u64)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32) |                         \
+          (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4);                                  \
+      g_join_stamps[(tile) * 16 + 11] = (u64)blockIdx.x + 1;                               \
+    }                                                                                      \
+  } while (0)
 #else
 #define JSTAMP(tile, k) \
   do {                  \
+  } while (0)
+#define JSTAMP_PLACE(tile) \
+  do {                     \
   } while (0)
 #endif
 
@@ -47,15 +63,18 @@ __device__ u64 g_join_stamps[65536 * 16];
 //   2. issue the loads of tile t + G into registers (they stream during the merge);
 //   3. merge tile t, block-scan its keep bits: count n_t and compaction list;
 //      publish n_t (an epoch-tagged 32-bit granule, written once), then issue the loads
-//      of stripe k-1's G tile counts;
-//   4. offsets of stripe k-1, computed redundantly by every workgroup from its G
-//      counts: tile (w + (k-1)G) starts at base_{k-1} + Σ_{w' < w} n, and
-//      base_k = base_{k-1} + Σ_{all w'} n;
+//      of the G tile counts before tile t - G, those of tiles [t - 2G, t - G);
+//   4. the offset of tile t - G: that of tile t - 2G plus those G counts.  They are the
+//      counts of the workgroups BELOW w in stripe k-1 and of w and the workgroups above it
+//      in stripe k-2 (dg_jstripe.h), so a workgroup waits for a prefix of the stripe it
+//      writes and takes the stripe's total a stripe late: workgroup 0 never waits for the
+//      current stripe, and one late workgroup holds up those above it, not the grid;
 //   5. write tile t - G's kept rows (still in buffer (k-1)%2), coalesced, at that
 //      offset.
-// No look-back chain and no ticket: a stripe's counts were all published one merge
-// earlier, so step 4 rarely waits; its cost is one G-word read per iteration, issued
-// behind the tile's own count.  Spins stay bounded (scan.err bit 0 on timeout).
+// No look-back chain and no ticket: the counts below w were published one merge earlier
+// and the others two, so step 4 rarely waits; its cost is one G-word read per iteration,
+// issued behind the tile's own count.  Every wait points at a strictly earlier tile.  Spins
+// stay bounded (scan.err bit 0 on timeout).
 // (stripe_sums' partials are double-buffered by iteration parity, which drops the barrier
 // a single buffer needs before its writes: measured neutral, config 5 356-360 vs 358-360 us
 // and config 2 34.5-35.4 vs 34.6-34.7 us, rocprofv3 on one box; kept, one barrier fewer)
@@ -68,7 +87,7 @@ struct StreamLds {
   u64 kslice[2][KEYED ? KS : 1];    // keyed: the tile's keyset slice (<= KS entries)
   u64 kspl[KEYED ? 2 * FUSE_IT : 1];  // keyed + fused: keyset splits of this workgroup's tiles
   u32 wave[JB / WAVE + 1];
-  u64 red[2][2 * (JB / WAVE)];  // stripe_sums' wave partials, double-buffered by iteration parity
+  u64 red[2][JB / WAVE];  // stripe_sums' wave partials, double-buffered by iteration parity
   u64 spl[2 * FUSE_IT];  // fused: splits of this workgroup's tiles (start, end per tile)
   u64 chk[JB / WAVE];    // CHG: each wave's last change event, and 1 + its lane (0: none)
   int chf[JB / WAVE];
@@ -81,26 +100,22 @@ __device__ __forceinline__ void publish_count(u32* cs, u64 t, u32 epoch, u32 n) 
   __hip_atomic_store(cs + t, (epoch << CNT_BITS) | n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Stripe counts of tiles [base_t, base_t + G) ∩ [0, ntiles), CQ per thread: issued
-// behind the tile's own count (stripe_load), consumed after the barrier that follows
-// (stripe_sums), which re-polls the ones not yet published and returns (Σ over workgroups
-// w' < w, Σ over all).
+// The G counts a workgroup awaits before it writes tile t, those of tiles [t - G, t)
+// (dg_jstripe.h: the positions below its own in t's stripe, the rest of the stripe before),
+// CQ per thread: issued behind the tile's own count (stripe_load), consumed after the
+// barrier that follows (stripe_sums), which re-polls the ones not yet published and returns
+// their sum, tile t's offset less that of the workgroup's previous tile.
 struct StripeCounts {
   u32 v[CQ];
-  bool ready;
 };
 
-__device__ __forceinline__ void stripe_load(const u32* cs, u64 base_t, u64 G, u64 ntiles, u32 epoch,
-                                            StripeCounts& c) {
-  c.ready = true;
+__device__ __forceinline__ void stripe_load(const u32* cs, u64 t, u64 G, StripeCounts& c) {
 #pragma unroll
   for (int q = 0; q < CQ; q++) {
-    const u64 x = (u64)threadIdx.x + (u64)q * JB;  // workgroup index within the stripe
-    // (every lane loads: an absent tile reads the stripe's first granule, base_t < ntiles;
-    // stripe_sums replaces what it read -- here the select would wait for the load)
-    const bool has = x < G && base_t + x < ntiles;
-    c.v[q] = __hip_atomic_load(cs + base_t + (has ? x : 0), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+    // (every lane loads: one without a granule reads tile t's own; stripe_sums replaces
+    // what it read -- here the select would wait for the load)
+    const StripeSlot sl = stripe_slot(G, t, (u64)threadIdx.x + (u64)q * JB);
+    c.v[q] = __hip_atomic_load(cs + sl.tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -109,9 +124,10 @@ __device__ __forceinline__ void stripe_load(const u32* cs, u64 base_t, u64 G, u6
 // resident until it finishes, so the wait ends; one that has not (another stream's or
 // process's kernels hold the CUs) makes the waiter raise the abort flag after
 // ABORT_POLLS, and the grid runs on without waiting (err bit 2; the caller re-runs the
-// join on the two-pass kernels).  Each workgroup stores its start flag once: no
-// contended counter at launch.
+// join on the two-pass kernels).  Each workgroup stores its start flag once, at its stripe
+// position: no contended counter at launch.
 constexpr u32 ABORT_POLLS = 1u << 13;
+constexpr int STAGGER_SLEEP = 10;  // s_sleep units (64 clocks each) per step of DG_JOIN_STAGGER
 
 // The check's own arguments are read from the kernel-argument segment where they are
 // used (volatile: not hoisted), so they hold no registers across the tile loop.
@@ -125,8 +141,9 @@ __device__ __forceinline__ const Scan* cold_scan() {
 }
 
 // Whether this thread stops waiting: the grid has aborted, or (after ABORT_POLLS) a
-// workgroup whose count it still lacks has not started.
-__device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 need, const StripeCounts& c) {
+// workgroup whose count it still lacks has not started.  (A lane without a granule holds
+// the epoch's tag since stripe_sums replaced its value, so it lacks nothing.)
+__device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 t, u64 G, const StripeCounts& c) {
   const Scan* sc = cold_scan();
   u32* abort = cold(&sc->abort);
   if (__hip_atomic_load(abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) return true;
@@ -135,9 +152,10 @@ __device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 need, const
   bool absent = false;
 #pragma unroll
   for (int q = 0; q < CQ; q++) {
-    const u64 x = (u64)threadIdx.x + (u64)q * JB;
-    if (x < need && (c.v[q] >> CNT_BITS) != epoch &&
-        __hip_atomic_load(started + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch)
+    if ((c.v[q] >> CNT_BITS) == epoch) continue;
+    const StripeSlot sl = stripe_slot(G, t, (u64)threadIdx.x + (u64)q * JB);
+    if (__hip_atomic_load(started + stripe_position(G, sl.tile), __ATOMIC_RELAXED,
+                          __HIP_MEMORY_SCOPE_AGENT) != epoch)
       absent = true;
   }
   if (!absent) return false;
@@ -151,25 +169,18 @@ __device__ __forceinline__ bool grid_check(u32 epoch, u32 spins, u64 need, const
 // After an abort the counts not yet published read as 0, so the rest of the grid runs
 // through its tiles without waiting and writes stay inside the output (whose rows the
 // caller discards).
-__device__ __forceinline__ void stripe_sums(const u32* cs, u32 epoch, u32* err, u64 base_t,
-                                            u64 G, u64 ntiles, u64 w, bool need_all,
-                                            StripeCounts& c, u64* s_red, u64* below, u64* all) {
+__device__ __forceinline__ u64 stripe_sums(u32 epoch, u32* err, u64 t, u64 G, StripeCounts& c,
+                                           u64* s_red) {
   const int tid = threadIdx.x;
 #pragma unroll
-  for (int q = 0; q < CQ; q++) {  // absent tiles count 0
-    const u64 x = (u64)tid + (u64)q * JB;
-    c.v[q] = x < G && base_t + x < ntiles ? c.v[q] : epoch << CNT_BITS;
-  }
-  // counts this workgroup needs: all of the stripe's (for the next stripe's base), or
-  // only those of the workgroups below it (its last tile: no next stripe)
-  const u64 need = need_all ? G : w;
+  for (int q = 0; q < CQ; q++)  // lanes without a granule count 0
+    if (!stripe_slot(G, t, (u64)tid + (u64)q * JB).has) c.v[q] = epoch << CNT_BITS;
   for (u32 spins = 0;; spins++) {  // (rare) wait for counts not yet published
     bool ready = true;
 #pragma unroll
-    for (int q = 0; q < CQ; q++)
-      ready &= (u64)tid + (u64)q * JB >= need || (c.v[q] >> CNT_BITS) == epoch;
+    for (int q = 0; q < CQ; q++) ready &= (c.v[q] >> CNT_BITS) == epoch;
     if (ready) break;
-    if ((spins & 63) == 63 && grid_check(epoch, spins, need, c)) {
+    if ((spins & 63) == 63 && grid_check(epoch, spins, t, G, c)) {
 #pragma unroll
       for (int q = 0; q < CQ; q++)
         if ((c.v[q] >> CNT_BITS) != epoch) c.v[q] = epoch << CNT_BITS;
@@ -181,45 +192,31 @@ __device__ __forceinline__ void stripe_sums(const u32* cs, u32 epoch, u32* err, 
     }
     __builtin_amdgcn_s_sleep(2);
     // (the granules' address again from the argument segment, as grid_check reads its own:
-    // the lane's address into `cs` otherwise holds a register pair across the tile loop for
-    // this rare path, which the keyed kernels with change events spill)
+    // the lane's address into the granules otherwise holds a register pair across the tile
+    // loop for this rare path, which the keyed kernels with change events spill)
     const u32* cs_poll = cold(&cold_scan()->counts);
 #pragma unroll
-    for (int q = 0; q < CQ; q++) {
-      const u64 x = (u64)tid + (u64)q * JB;
-      if (x < need && (c.v[q] >> CNT_BITS) != epoch)
-        c.v[q] = __hip_atomic_load(cs_poll + base_t + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    for (int q = 0; q < CQ; q++)
+      if ((c.v[q] >> CNT_BITS) != epoch)
+        c.v[q] = __hip_atomic_load(cs_poll + stripe_slot(G, t, (u64)tid + (u64)q * JB).tile,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  u64 lo = 0, tot = 0;
+  u32 tot = 0;
 #pragma unroll
-  for (int q = 0; q < CQ; q++) {
-    const u64 x = (u64)tid + (u64)q * JB;
-    const u64 n = c.v[q] & ((1u << CNT_BITS) - 1);
-    tot += n;
-    lo += x < w ? n : 0;
-  }
-  // (a wave's sums of <= 2 x 64 twelve-bit counts fit 32 bits: DPP reductions)
-  lo = wave_sum_u32((u32)lo);
-  tot = wave_sum_u32((u32)tot);
+  for (int q = 0; q < CQ; q++) tot += c.v[q] & ((1u << CNT_BITS) - 1);
+  // (a wave's sum of <= 2 x 64 twelve-bit counts fits 32 bits: a DPP reduction)
+  tot = wave_sum_u32(tot);
   constexpr int NW = JB / WAVE;
   // (no barrier before the writes: the caller alternates two s_red buffers by iteration
   // parity, and the previous reader of this buffer finished two iterations ago, behind the
   // iterations' own barriers)
-  if ((tid & (WAVE - 1)) == 0) {
-    s_red[tid / WAVE] = lo;
-    s_red[NW + tid / WAVE] = tot;
-  }
+  if ((tid & (WAVE - 1)) == 0) s_red[tid / WAVE] = tot;
   __syncthreads();
-  lo = 0;
-  tot = 0;
+  u32 sum = 0;  // (<= CQ * JB counts below 2^CNT_BITS)
 #pragma unroll
-  for (int i = 0; i < NW; i++) {
-    lo += s_red[i];
-    tot += s_red[NW + i];
-  }
-  *below = lo;
-  *all = tot;
+  for (int i = 0; i < NW; i++) sum += (u32)s_red[i];
+  // (uniform, and said so: the offset it is added to then lives in scalar registers)
+  return (u32)__builtin_amdgcn_readfirstlane((int)sum);
 }
 
 template <bool KEYED>
@@ -246,6 +243,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     __hip_atomic_store(cold(&cold_scan()->started) + w, epoch, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   if (w < G) JSTAMP(w, 0);  // (stamps build: slot 0 of a workgroup's first tile = its entry)
+  if (w < G) JSTAMP_PLACE(w);
   Staged r;
   u64 ga0 = 0, ga1 = 0;  // fused: the first tile's speculative splits
   if (LATE) {
@@ -339,10 +337,33 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     vv_far = fill_vv_tables(p.ca, p.cb, s.tab[0], s.tab[1]);  // once per workgroup
     if (LATE) vv_far = __syncthreads_or(vv_far);
   }
-  u64 base = 0;  // output offset of the first tile of the current stripe
+  // DG_JOIN_STAGGER (default 0: measured and not kept): the upper half of the
+  // stripe starts its tiles later by that many sleeps of about a quarter microsecond.  The
+  // two workgroups of a CU are observed to sit in opposite halves (w and w + 256 on 256
+  // CUs: speed only, nothing depends on it).  A bounded sleep: it waits on nothing, and
+  // behind a long one the lower half meets the wait for the stripe before (the tests).
+  if (2 * w >= G)  // (the upper half: `upper` below)
+    for (int i = cold(&((const JoinArgs*)__builtin_amdgcn_kernarg_segment_ptr())->stagger); i > 0; i--)
+      __builtin_amdgcn_s_sleep(STAGGER_SLEEP);
+  u64 off = 0;  // output offset of this workgroup's previous tile (of tile w: the counts below it)
   u32 np = 0;    // kept rows of this workgroup's tile of the previous stripe
+  // The two workgroups of a CU do not run at one pace: the upper half of every stripe
+  // (observed: w + 256 sits beside w on 256 CUs) took 25 % longer per iteration, then ran its
+  // last tiles alone on the CU.  Supposed, not measured: at equal priority the CU issues from
+  // its older waves first, and the upper half is dispatched second.  The upper half raises
+  // its waves' priority on every second iteration, which evens the two out (config 2
+  // 31.9 -> 29.3-29.6 us per join, config 5 313 -> 285-291; always raised, the lower half
+  // falls behind instead: 34.1-34.6).  Speed only: nothing depends on which workgroups share
+  // a CU.
+  const bool upper = 2 * w >= G;
   for (int k = 0;; k++) {
     const int bi = k & 1;
+    if (upper) {
+      if (k & 1)
+        __builtin_amdgcn_s_setprio(1);
+      else
+        __builtin_amdgcn_s_setprio(0);
+    }
     if (k > 0) JSTAMP(t, 0);
     JSTAMP(t, 1);
     commit_tile(r, s.buf[bi]);
@@ -405,7 +426,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     // 33.0-34.0 after the merge and 33.5-33.8 here (parent 34.2-35.2; A/B on one box).
     // (With change events they are loaded behind that block, not held across it.)
     StripeCounts sc;
-    if (!CHG && k > 0) stripe_load(cs, t - G - w, G, ntiles, epoch, sc);
+    if (!CHG && k > 0) stripe_load(cs, t - G, G, sc);
     __syncthreads();
     if (CHG) {  // the tile's change events (keys, ascending, repeats allowed) -> chg_tmp,
                 // with the per-tile figures the changed-key kernels need (chg_sum/write)
@@ -462,27 +483,22 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       }
       if (ne && p0 == 0) p.chg_fk[t] = fkey;
       if (ne && p2 == n2) p.chg_lk[t] = lkey;
-      if (k > 0) stripe_load(cs, t - G - w, G, ntiles, epoch, sc);
+      if (k > 0) stripe_load(cs, t - G, G, sc);
     }
     JSTAMP(t, 4);
     if (k > 0) {  // stripe k-1: this workgroup's tile t - G
-      u64 below, all;
-      stripe_sums(cs, epoch, p.scan.err, t - G - w, G, ntiles, w, true, sc, s.red[k & 1], &below,
-                  &all);
+      off += stripe_sums(epoch, p.scan.err, t - G, G, sc, s.red[k & 1]);
       JSTAMP(t, 5);
-      write_tile(p, s, bi ^ 1, base + below, np);
-      base += all;
+      write_tile(p, s, bi ^ 1, off, np);
     }
     JSTAMP(t, 6);
     np = n;
     if (tn >= ntiles) {
-      u64 below, all;
-      StripeCounts last;
-      stripe_load(cs, t - w, G, ntiles, epoch, last);
-      stripe_sums(cs, epoch, p.scan.err, t - w, G, ntiles, w, false, last, s.red[(k + 1) & 1],
-                  &below, &all);
-      write_tile(p, s, bi, base + below, np);
-      if (tid == 0 && t == ntiles - 1) p.d_count[0] = base + below + np;
+      StripeCounts last;  // its last tile: the same sum, a stripe earlier than the others'
+      stripe_load(cs, t, G, last);
+      off += stripe_sums(epoch, p.scan.err, t, G, last, s.red[(k + 1) & 1]);
+      write_tile(p, s, bi, off, np);
+      if (tid == 0 && t == ntiles - 1) p.d_count[0] = off + np;
       break;
     }
     t = tn;

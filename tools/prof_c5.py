@@ -33,7 +33,7 @@ for _ in range(reps):
 eng.sync()
 dt = (time.perf_counter() - t0) / reps
 n_out = int(d_counts[0].item())
-print(f"config5 rows_in={sa.n + sb.n} rows_out={n_out} {dt * 1e3:.3f} ms/join "
+print(f"config{2 if os.environ.get('C5_CONFIG') == '2' else 5} rows_in={sa.n + sb.n} rows_out={n_out} {dt * 1e3:.3f} ms/join "
       f"{36 * (sa.n + sb.n + n_out) / dt / 1e12:.2f} TB/s", flush=True)
 if os.environ.get("C5_STAMPS"):
     import ctypes as C
