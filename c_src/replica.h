@@ -183,6 +183,27 @@ uint64_t dgr_batch_pack(uint64_t* host, uint64_t* dev, int k, const dg_store* de
                         const uint64_t* const* keys, const uint64_t* n_keys, dg_store* rows_v,
                         dg_context* ctx_v, const uint64_t** keys_v, uint64_t* n_keys_v);
 
+/* dgr_mutate_batch[_diffs]' route, DGR_MUTATE_ROUTE in the environment at dgr_engine_open: `home`
+ * (the default: faster on every shape measured) tries dg_mutate_home on the packed
+ * message for batches of at most 512 ops on a state whose context is a version vector, and runs
+ * the copy, dg_mutate_batch and the join where that declines; `batch` is that sequence alone.
+ * The same results either way.
+ * How often this engine's dgr_mutate_batch[_diffs] tried dg_mutate_home, was served by it, and
+ * was declined (DG_HOME_FALLBACK: the copy, dg_mutate_batch and the join then ran):
+ * out[DGR_MUTATE_TRIED], out[DGR_MUTATE_SERVED], out[DGR_MUTATE_DECLINED].  For tests and A/B. */
+enum { DGR_MUTATE_TRIED = 0, DGR_MUTATE_SERVED = 1, DGR_MUTATE_DECLINED = 2 };
+int dgr_mutate_route_stats(const dgr_engine* g, uint64_t out[3]);
+
+/* dgr_mutate_batch's packed message, host code only (c_src/test_mutate_pack.c checks them).
+ * dgr_mutate_words: its length in 8-byte words, 4 m + ceil(m / 8).  dgr_mutate_pack: the m ops
+ * (batch order) written to `host` as key | val | ts | add_rank (m words each) and kind (m bytes
+ * behind them), stably sorted by key -- equal keys keep batch order -- with add_rank = the adds
+ * before the op in the batch and a remove's val and ts zero; *n_adds = the batch's adds.
+ * DG_E_NOMEM or DG_OK. */
+uint64_t dgr_mutate_words(uint64_t m);
+int dgr_mutate_pack(uint64_t* host, uint64_t m, const uint8_t* kind, const uint64_t* key, const uint64_t* val,
+                    const int64_t* ts, uint64_t* n_adds);
+
 /* read/1 (all != 0) or read/2 of `keys` (host ids, any order) (aw_lww_map.ex:211-224):
  * the winning value id per key, ascending by key id.  Host views. */
 int dgr_read(dgr_state* s, uint64_t version, int all, const uint64_t* keys, uint64_t n_keys,

@@ -89,9 +89,14 @@ struct dgr_engine {
    * often it tried dg_join_deltas_keyed, was served and was declined (dgr_deltas_route_stats) */
   int deltas_route;
   uint64_t keyed_stats[3];
+  /* dgr_mutate_batch's route (DGR_MUTATE_ROUTE=batch|home, read at engine open), and how often
+   * it tried dg_mutate_home, was served and was declined (dgr_mutate_route_stats) */
+  int mutate_route;
+  uint64_t mutate_stats[3];
 };
 
 enum { DGR_ROUTE_AUTO = 0, DGR_ROUTE_STREAM = 1, DGR_ROUTE_KEYED = 2 };
+enum { DGR_MROUTE_BATCH = 0, DGR_MROUTE_HOME = 1 };
 
 #define TRY(x)                     \
   do {                             \

@@ -36,6 +36,8 @@ static int small_fits(const dgr_state* s, const dg_store* drows, const dg_contex
   return n_keys <= 512 && drows->n <= 512 && dctx->n <= 1024 && s->ctx.kind == DG_CTX_VV;
 }
 
+static void home_views(dgr_state* s, dgr_changed* out, dgr_diffs* diffs);
+
 static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dctx, const uint64_t* dkeys,
                        uint64_t n_keys, dgr_changed* out, dgr_diffs* diffs, int* done) {
   dgr_engine* g = s->g;
@@ -55,6 +57,13 @@ static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dc
   if (h[0] & DG_HOME_FALLBACK) return DG_OK;
   s->version++;
   *done = 1;
+  home_views(s, out, diffs);
+  return DG_OK;
+}
+
+/* the result block of a served home call (the join's or the mutation's) as the caller's views */
+static void home_views(dgr_state* s, dgr_changed* out, dgr_diffs* diffs) {
+  uint64_t* h = s->g->h_home;
   out->version = s->version;
   out->n_changed = h[1];
   out->keys = h + DG_HOME_KEYS;
@@ -62,7 +71,6 @@ static int apply_small(dgr_state* s, const dg_store* drows, const dg_context* dc
   out->ctx = rp_ctx(h + DG_HOME_CTX, DG_HOME_NODES, DG_CTX_VV, h[3], DG_HOME_NODES);
   if (diffs)
     *diffs = (dgr_diffs){h[1], h + DG_HOME_DIFF_OLD, h + DG_HOME_DIFF_NEW, (const uint8_t*)(h + DG_HOME_DIFF_FLAGS)};
-  return DG_OK;
 }
 
 /* The return block's views a join writes through: the changed keys' rows, the joined
@@ -313,15 +321,36 @@ int dgr_join_deltas_diffs(dgr_state* s, uint64_t version, int k, const dg_store*
   return diffs ? join_deltas(s, version, k, deltas, ctxs, keys, n_keys, out, diffs) : DG_E_INVAL;
 }
 
-typedef struct {
-  uint64_t key;
-  uint64_t idx;
-} kidx;
-
-static int cmp_kidx(const void* a, const void* b) { /* by key, then batch order: stable */
-  const kidx *x = (const kidx*)a, *y = (const kidx*)b;
-  if (x->key != y->key) return x->key < y->key ? -1 : 1;
-  return x->idx < y->idx ? -1 : x->idx > y->idx;
+/* Under the `home` route (g->mutate_route, DGR_MUTATE_ROUTE at engine open) a batch of at most
+ * 512 ops on a VV state first tries dg_mutate_home on the message where the host packed it
+ * (page-locked, mapped memory: no copy launch, no delta, one wait).  *done = 0: declined,
+ * nothing happened, and the copy, dg_mutate_batch and the join run as under `batch`. */
+static int mutate_home(dgr_state* s, uint32_t node, uint64_t m, uint64_t n_adds, dgr_changed* out,
+                       dgr_diffs* diffs, int* done) {
+  dgr_engine* g = s->g;
+  *done = 0;
+  if (g->mutate_route != DGR_MROUTE_HOME || m > 512 || s->ctx.kind != DG_CTX_VV) return DG_OK;
+  TRY(room_for(s, m, 1));
+  if (!g->h_home) TRY(dg_host_alloc(g->e, DG_HOME_DIFFS_WORDS * 8, (void**)&g->h_home));
+  uint64_t* h = g->h_msg;
+  int swapped = 0;
+  g->mutate_stats[DGR_MUTATE_TRIED]++;
+  const int rc = (diffs ? dg_mutate_home_diffs : dg_mutate_home)(
+      g->e, &s->rows, &s->ctx, node, m, (const uint8_t*)(h + 4 * m), h, h + m, (const int64_t*)(h + 2 * m),
+      h + 3 * m, n_adds, &s->spare, s->has_tree ? &s->tree : NULL, g->h_home, &swapped);
+  if (rc) {
+    s->version++;
+    return rc;
+  }
+  if (g->h_home[0] & DG_HOME_FALLBACK) {
+    g->mutate_stats[DGR_MUTATE_DECLINED]++;
+    return DG_OK;
+  }
+  g->mutate_stats[DGR_MUTATE_SERVED]++;
+  s->version++;
+  *done = 1;
+  home_views(s, out, diffs);
+  return DG_OK;
 }
 
 /* dgr_mutate_batch (diffs NULL) and dgr_mutate_batch_diffs */
@@ -331,43 +360,16 @@ static int mutate_batch(dgr_state* s, uint64_t version, uint32_t node, uint64_t 
   if (!s || !out || (m && (!kind || !key || !val || !ts))) return DG_E_INVAL;
   TRY(check_version(s, version));
   dgr_engine* g = s->g;
-  /* kind | key | val | ts | add_rank, sorted by key (batch order within a key), one copy */
-  kidx* ord = (kidx*)malloc((m ? m : 1) * sizeof *ord);
-  if (!ord) return DG_E_NOMEM;
-  for (uint64_t i = 0; i < m; i++) {
-    ord[i].key = key[i];
-    ord[i].idx = i;
-  }
-  qsort(ord, m, sizeof *ord, cmp_kidx);
-  int rc = ri_grow_msg(g, 4 * m + (m + 7) / 8 + 2);
-  if (rc) {
-    free(ord);
-    return rc;
-  }
+  /* key | val | ts | add_rank | kind, sorted by key (batch order within a key): ONE message */
+  const uint64_t words = dgr_mutate_words(m);
+  TRY(ri_grow_msg(g, words + 2));
   uint64_t* h = g->h_msg;
-  uint8_t* hk = (uint8_t*)(h + 4 * m);
   uint64_t n_adds = 0;
-  uint64_t* rank = (uint64_t*)malloc((m ? m : 1) * 8);
-  if (!rank) {
-    free(ord);
-    return DG_E_NOMEM;
-  }
-  for (uint64_t i = 0; i < m; i++) { /* the adds before each op, in batch order */
-    rank[i] = n_adds;
-    n_adds += kind[i] != 0;
-  }
-  for (uint64_t j = 0; j < m; j++) {
-    const uint64_t i = ord[j].idx;
-    h[j] = key[i];
-    h[m + j] = kind[i] ? val[i] : 0;
-    h[2 * m + j] = kind[i] ? (uint64_t)ts[i] : 0;
-    h[3 * m + j] = rank[i];
-    hk[j] = kind[i] != 0;
-  }
-  free(ord);
-  free(rank);
-  const uint64_t words = 4 * m + (m + 7) / 8;
-  TRY(dg_copy_async(g->e, g->d_msg, h, words * 8));
+  TRY(dgr_mutate_pack(h, m, kind, key, val, ts, &n_adds));
+  int done = 0, rc;
+  TRY(mutate_home(s, node, m, n_adds, out, diffs, &done));
+  if (done) return DG_OK;
+  TRY(dg_copy_async(g->e, g->d_msg, h, words * 8)); /* one copy */
   const uint64_t* d = g->d_msg;
   TRY(ri_grow_store(g, &g->mrows, umax(m, 1)));
   TRY(ri_grow(g, NULL, &g->mkeys, &g->mkeys_cap, umax(m, 1)));

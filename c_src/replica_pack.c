@@ -81,6 +81,54 @@ uint64_t rp_pack_ctx(uint64_t* hb, uint64_t* db, uint64_t o, const dg_context* c
   return o + ctx_words(n);
 }
 
+/* The packed message of a batch of m ops (dgr_mutate_batch): key | val | ts | add_rank, m words
+ * each, then the kinds, a byte each -- the ops stably sorted by key (batch order within a key),
+ * an add's rank the number of adds before it in the batch, a remove's value and ts zero. */
+uint64_t dgr_mutate_words(uint64_t m) { return 4 * m + (m + 7) / 8; }
+
+typedef struct {
+  uint64_t key;
+  uint64_t idx;
+} kidx;
+
+static int cmp_kidx(const void* a, const void* b) { /* by key, then batch order: stable */
+  const kidx *x = (const kidx*)a, *y = (const kidx*)b;
+  if (x->key != y->key) return x->key < y->key ? -1 : 1;
+  return x->idx < y->idx ? -1 : x->idx > y->idx;
+}
+
+int dgr_mutate_pack(uint64_t* host, uint64_t m, const uint8_t* kind, const uint64_t* key, const uint64_t* val,
+                    const int64_t* ts, uint64_t* n_adds) {
+  kidx* ord = (kidx*)malloc((m ? m : 1) * sizeof *ord);
+  uint64_t* rank = (uint64_t*)malloc((m ? m : 1) * 8);
+  if (!ord || !rank) {
+    free(ord);
+    free(rank);
+    return DG_E_NOMEM;
+  }
+  uint64_t adds = 0;
+  for (uint64_t i = 0; i < m; i++) { /* the adds before each op, in batch order */
+    ord[i].key = key[i];
+    ord[i].idx = i;
+    rank[i] = adds;
+    adds += kind[i] != 0;
+  }
+  qsort(ord, m, sizeof *ord, cmp_kidx);
+  uint8_t* hk = (uint8_t*)(host + 4 * m);
+  for (uint64_t j = 0; j < m; j++) {
+    const uint64_t i = ord[j].idx;
+    host[j] = key[i];
+    host[m + j] = kind[i] ? val[i] : 0;
+    host[2 * m + j] = kind[i] ? (uint64_t)ts[i] : 0;
+    host[3 * m + j] = rank[i];
+    hk[j] = kind[i] != 0;
+  }
+  free(ord);
+  free(rank);
+  *n_adds = adds;
+  return DG_OK;
+}
+
 /* The packed message of a batch of k deltas: per delta its rows | its context | its keyset
  * (sorted, unique, padded to an even number of words), every part at a 16-byte aligned
  * offset. */

@@ -243,6 +243,12 @@ _SIGS = {
                                         C.c_uint32, C.c_uint64, C.c_void_p, P64, P64, PI64, P64,
                                         C.c_uint64, C.POINTER(dg_store), C.POINTER(dg_context), P64,
                                         C.c_uint64, P64]),
+    "dg_mutate_home": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context), C.c_uint32,
+                                 C.c_uint64, C.c_void_p, P64, P64, PI64, P64, C.c_uint64,
+                                 C.POINTER(dg_store), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "dg_mutate_home_diffs": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context), C.c_uint32,
+                                       C.c_uint64, C.c_void_p, P64, P64, PI64, P64, C.c_uint64,
+                                       C.POINTER(dg_store), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dg_join2_async": (C.c_int, [C.c_void_p, C.POINTER(dg_store), C.POINTER(dg_context),
                                  C.POINTER(dg_store), C.POINTER(dg_context), P64, C.c_uint64,
                                  C.POINTER(dg_store), C.POINTER(dg_context), P64]),

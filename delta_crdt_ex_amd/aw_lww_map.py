@@ -269,12 +269,10 @@ def merkle_diff(a: AWLWWMap, ta: MerkleTree, b: AWLWWMap, tb: MerkleTree, cap: i
     return out
 
 
-def mutate_batch(ops, node_id, state: AWLWWMap):
-    """Many add/4 and remove/3 calls by one node as ONE delta on the GPU
-    (dg_mutate_batch; SURVEY §8(f).3): ops = [("add", key, value[, ts]) or ("remove",
-    key)] in order.  Returns (delta, keys): join(state, delta, keys) equals applying the
-    ops one by one as CausalCrdt does.  The state's context must be a version vector
-    (compress_dots/1, as CausalCrdt keeps it)."""
+def marshal_ops(ops, node_id, state: AWLWWMap):
+    """ops = [("add", key, value[, ts]) or ("remove", key)] in batch order as the arrays
+    Engine.mutate_batch and Engine.mutate_home take: (node id, (kind, key, val, ts, add_rank)
+    on the device, stably sorted by key id, n_adds)."""
     U = state.universe
     nid = U.node(node_id)
     m = len(ops)
@@ -300,9 +298,19 @@ def mutate_batch(ops, node_id, state: AWLWWMap):
     def d(a, view):
         return torch.from_numpy(np.ascontiguousarray(a[order]).view(view)).to(dev)
 
-    delta, dots, keys = engine().mutate_batch(
-        state.rows, state.ctx, nid, torch.from_numpy(kind[order]).to(dev), d(key, np.int64),
-        d(val, np.int64), d(ts, np.int64), d(rank, np.int64), int(kind.sum()))
+    return nid, (torch.from_numpy(kind[order]).to(dev), d(key, np.int64), d(val, np.int64), d(ts, np.int64),
+                 d(rank, np.int64)), int(kind.sum())
+
+
+def mutate_batch(ops, node_id, state: AWLWWMap):
+    """Many add/4 and remove/3 calls by one node as ONE delta on the GPU
+    (dg_mutate_batch; SURVEY §8(f).3): ops = [("add", key, value[, ts]) or ("remove",
+    key)] in order.  Returns (delta, keys): join(state, delta, keys) equals applying the
+    ops one by one as CausalCrdt does.  The state's context must be a version vector
+    (compress_dots/1, as CausalCrdt keeps it)."""
+    U = state.universe
+    nid, arrays, n_adds = marshal_ops(ops, node_id, state)
+    delta, dots, keys = engine().mutate_batch(state.rows, state.ctx, nid, *arrays, n_adds)
     return AWLWWMap(delta, dots, U), [U.key_term(int(k)) for k in u64(keys)]
 
 

@@ -219,5 +219,34 @@ def apply_ops(state: M.AWLWWMap, ops, node_id):
     return update_state_with_delta(state, delta, keys)
 
 
+def update_resident_state_with_ops(state: M.AWLWWMap, ops, node_id, spare: Store, tree=None, journal=None):
+    """apply_ops on a state that stays resident: the ops (M.mutate_batch's) are applied to
+    `state` itself as update_resident_state_with_delta applies their delta, and the same
+    `diffs` value is returned -- over the touched keys in ascending key-id order, as apply_ops
+    lists them -- with the same journal record.  A batch of at most 512 ops goes down as ONE
+    launch and wait (Engine.mutate_home_diffs: the delta is built and joined on the device and
+    its dot list never made); a batch the library declines has touched nothing and takes
+    M.mutate_batch and update_resident_state_with_delta."""
+    U = state.universe
+    nid, arrays, n_adds = M.marshal_ops(ops, node_id, state)
+    eng = M.engine()
+    home = None
+    if len(ops) <= HOME_KEYS:
+        _make_room(state, spare, 1, len(ops))
+        home = eng.mutate_home_diffs(state.rows, state.ctx, nid, *arrays, n_adds, spare, tree)
+    if home is None:
+        delta, dots, keys = eng.mutate_batch(state.rows, state.ctx, nid, *arrays, n_adds)
+        return update_resident_state_with_delta(state, M.AWLWWMap(delta, dots, U),
+                                                [U.key_term(int(k)) for k in u64(keys)], spare, tree, journal)
+    state._host = None
+    changed, (old_val, new_val, flags) = home[0], home[4]
+    if journal is not None:
+        _journal_effect(journal, state, tree, changed, home[1], home[2])
+    if len(changed) == 0:
+        return None
+    order = [(int(k), U.key_term(int(k))) for k in np.unique(u64(arrays[1]))]
+    return _callback_diffs(U, order, changed, old_val, new_val, flags)
+
+
 __all__ = ["update_state_with_delta", "update_resident_state_with_delta",
-           "update_resident_state_with_deltas", "apply_ops"]
+           "update_resident_state_with_deltas", "apply_ops", "update_resident_state_with_ops"]

@@ -383,35 +383,62 @@ static_assert(SMALL_O_KEYS == DG_HOME_KEYS &&SMALL_O_ROWS == DG_HOME_ROWS && SMA
                   SMALL_O_CTX == DG_HOME_CTX && SMALL_NODES == DG_HOME_NODES && SMALL_WORDS == DG_HOME_WORDS &&
                   SMALL_FALLBACK == DG_HOME_FALLBACK,
               "the result block is the header's home layout");
+static_assert(SMALL_PUB_TOUCHED > 16 && SMALL_PUB_TOUCHED < CONT_HOME, "a free word of the publish block");
 static_assert(SMALL_O_DOLD == DG_HOME_DIFF_OLD && SMALL_O_DNEW == DG_HOME_DIFF_NEW &&
                   SMALL_O_DFLAGS == DG_HOME_DIFF_FLAGS && SMALL_DIFFS_WORDS == DG_HOME_DIFFS_WORDS &&
                   KD_DIFF_OLD == DG_DIFF_OLD && KD_DIFF_NEW == DG_DIFF_NEW,
               "the diff ranges behind it are the header's");
 
-// dg_join_delta_home (diffs false) and dg_join_delta_home_diffs: one body, two kernels
+// dg_mutate_home's ops (dg_mutate_batch's arrays): the delta and the keyset the kernel builds
+struct MutOps {
+  u32 node;
+  u64 m;
+  const uint8_t* kind;
+  const u64 *key, *val;
+  const i64* ts;
+  const u64* rank;
+  u64 n_adds;
+};
+
+// dg_join_delta_home (diffs false) and dg_join_delta_home_diffs: one body, two kernels; and
+// with `mu` (delta, delta_ctx and keys null) dg_mutate_home[_diffs]: the same body on the
+// kernels' mutation form, the keyset being at most mu->m keys the kernel leaves in scratch
 static int join_delta_home_impl(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,
                                 const dg_context* delta_ctx, const uint64_t* keys, uint64_t n_keys,
-                                dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped, bool diffs) {
+                                dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped, bool diffs,
+                                const MutOps* mu = nullptr) {
+  const char* const what = mu ? "dg_mutate_home" : "dg_join_delta_home";
   if (!e) return fail(DG_E_INVAL, "null engine");
-  if (!swapped || !spare || !state || !state_ctx || !home)
-    return fail(DG_E_INVAL, "dg_join_delta_home: null argument");
+  if (!swapped || !spare || !state || !state_ctx || !home) return fail(DG_E_INVAL, "%s: null argument", what);
   *swapped = 0;
   home[HW_FLAGS] = SMALL_FALLBACK;
-  TRY(check_store(state, "dg_join_delta_home state"));
-  TRY(check_store(delta, "dg_join_delta_home delta"));
-  TRY(check_ctx(state_ctx, "dg_join_delta_home state_ctx"));
-  TRY(check_ctx(delta_ctx, "dg_join_delta_home delta_ctx"));
-  if (tree) TRY(check_merkle(tree, "dg_join_delta_home tree"));
-  if (keys == nullptr && n_keys != 0) return fail(DG_E_INVAL, "dg_join_delta_home: keys NULL with n_keys>0");
-  const bool small = n_keys <= SMALL_KEYS && delta->n <= SMALL_DELTA && delta_ctx->n <= SMALL_DCTX &&
-                     state_ctx->kind == DG_CTX_VV && state_ctx->n <= SMALL_NODES &&
-                     spare->cap >= state->n + delta->n && state_ctx->cap >= 1 &&
-                     pair_aligned(state->key, state->val, state->ts, state->node, state->cnt) &&
-                     pair_aligned(spare->key, spare->val, spare->ts, spare->node, spare->cnt);
+  bool small;
+  if (mu) {
+    TRY(check_store(state, "dg_mutate_home state"));
+    TRY(check_ctx(state_ctx, "dg_mutate_home state_ctx"));
+    if (tree) TRY(check_merkle(tree, "dg_mutate_home tree"));
+    if (mu->m && (!mu->kind || !mu->key || !mu->val || !mu->ts || !mu->rank))
+      return fail(DG_E_INVAL, "dg_mutate_home: null argument");
+    if (mu->n_adds > mu->m) return fail(DG_E_INVAL, "dg_mutate_home: n_adds > m");
+    // (the touched keys are counted on the device: the kernel holds spare->cap against them)
+    small = mu->m <= SMALL_KEYS && mu->node < SMALL_NODES && state_ctx->cap >= state_ctx->n + 1;
+  } else {
+    TRY(check_store(state, "dg_join_delta_home state"));
+    TRY(check_store(delta, "dg_join_delta_home delta"));
+    TRY(check_ctx(state_ctx, "dg_join_delta_home state_ctx"));
+    TRY(check_ctx(delta_ctx, "dg_join_delta_home delta_ctx"));
+    if (tree) TRY(check_merkle(tree, "dg_join_delta_home tree"));
+    if (keys == nullptr && n_keys != 0) return fail(DG_E_INVAL, "dg_join_delta_home: keys NULL with n_keys>0");
+    small = n_keys <= SMALL_KEYS && delta->n <= SMALL_DELTA && delta_ctx->n <= SMALL_DCTX &&
+            spare->cap >= state->n + delta->n && state_ctx->cap >= 1;
+  }
+  small = small && state_ctx->kind == DG_CTX_VV && state_ctx->n <= SMALL_NODES && spare->cap >= state->n &&
+          pair_aligned(state->key, state->val, state->ts, state->node, state->cnt) &&
+          pair_aligned(spare->key, spare->val, spare->ts, spare->node, spare->cnt);
   if (!small) return DG_OK;  // home[0] = SMALL_FALLBACK: the caller takes dg_join_delta_rows
   TRY(set_device(e));
   TRY(settle(e));
-  const u64 nk = n_keys, a_tiles = splice_tiles(state->n);
+  const u64 nk = mu ? mu->m : n_keys, a_tiles = splice_tiles(state->n);
   const bool copy_now = a_tiles <= SMALL_COPY_TILES;
   HomeScratch h;
   TRY(carve(e, &e->sml, [&](Arena& m) { return home_layout(m, SMALL_EDIT, nk, a_tiles, SMALL_WORDS); }, &h));
@@ -425,10 +452,24 @@ static int join_delta_home_impl(dg_engine* e, dg_store* state, dg_context* state
   p.ca_node = state_ctx->node;
   p.ca_cnt = state_ctx->cnt;
   p.ca_cap = state_ctx->cap;
-  p.d = rows_of(delta);
-  p.cd = ctx_of(delta_ctx);
-  p.keys = keys;
-  p.nk = nk;
+  if (mu) {
+    keys = h.keys;
+    p.m_kind = mu->kind;
+    p.m_key = mu->key;
+    p.m_val = mu->val;
+    p.m_ts = mu->ts;
+    p.m_rank = mu->rank;
+    p.m = mu->m;
+    p.n_adds = mu->n_adds;
+    p.node = mu->node;
+    p.sp_cap = spare->cap;
+    p.keys_out = h.keys;
+  } else {
+    p.d = rows_of(delta);
+    p.cd = ctx_of(delta_ctx);
+    p.keys = keys;
+    p.nk = nk;
+  }
   p.e = rows_out_of(&ed);
   p.a_lo = a_lo;
   p.a_off = a_off;
@@ -443,7 +484,7 @@ static int join_delta_home_impl(dg_engine* e, dg_store* state, dg_context* state
   p.d_counts = e->d_counts;
   p.h_pub = e->d_pub;
   p.seq = ++e->pub_seq;
-  HIP_TRY(launch_small_delta(p, diffs, e->stream));
+  HIP_TRY(mu ? launch_small_mutate(p, diffs, e->stream) : launch_small_delta(p, diffs, e->stream));
   if (copy_now) {  // the moved rows' copy into the spare (if they moved: else it returns)
     SmallTailArgs ta{};
     ta.a = rows_of(state);
@@ -478,9 +519,14 @@ static int join_delta_home_impl(dg_engine* e, dg_store* state, dg_context* state
   sp.out = rows_out_of(spare);
   sp.run_if = res + HW_MOVED;  // (0 also when the join fell back or failed)
   const u64 flags = home[HW_FLAGS];
+  if (flags & SMALL_ORDER) {  // (the mutation form) nothing written
+    home[HW_FLAGS] = SMALL_FALLBACK;
+    return fail(DG_E_ORDER, "%s: ops are not sorted by key", what);
+  }
   if (flags & SMALL_FALLBACK) return DG_OK;  // nothing written: the general path
-  if (flags & MERKLE_INPUT_ERR) return tree_input_error((u32)flags, "dg_join_delta_home", "would hold");
+  if (flags & MERKLE_INPUT_ERR) return tree_input_error((u32)flags, what, "would hold");
   const u64 n_e = home[HW_EDIT], n_ak = home[HW_TAKEN];
+  if (mu) sp.nk = e->h_pub[SMALL_PUB_TOUCHED];  // the touched keys, counted by the kernel
   if (home[HW_MOVED]) {  // rows moved: the state is in `spare` (copied behind the join, or now)
     if (!copy_now) {
       HIP_TRY(launch_splice_index(sp, e->stream));
@@ -510,6 +556,24 @@ int dg_join_delta_home_diffs(dg_engine* e, dg_store* state, dg_context* state_ct
                              dg_store* spare, dg_merkle* tree, uint64_t* home, int* swapped) {
   return join_delta_home_impl(e, state, state_ctx, delta, delta_ctx, keys, n_keys, spare, tree, home, swapped,
                               true);
+}
+
+int dg_mutate_home(dg_engine* e, dg_store* state, dg_context* state_ctx, uint32_t node, uint64_t m,
+                   const uint8_t* kind, const uint64_t* key, const uint64_t* val, const int64_t* ts,
+                   const uint64_t* add_rank, uint64_t n_adds, dg_store* spare, dg_merkle* tree, uint64_t* home,
+                   int* swapped) {
+  const MutOps mu{node, m, kind, key, val, ts, add_rank, n_adds};
+  return join_delta_home_impl(e, state, state_ctx, nullptr, nullptr, nullptr, 0, spare, tree, home, swapped, false,
+                              &mu);
+}
+
+int dg_mutate_home_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, uint32_t node, uint64_t m,
+                         const uint8_t* kind, const uint64_t* key, const uint64_t* val, const int64_t* ts,
+                         const uint64_t* add_rank, uint64_t n_adds, dg_store* spare, dg_merkle* tree,
+                         uint64_t* home, int* swapped) {
+  const MutOps mu{node, m, kind, key, val, ts, add_rank, n_adds};
+  return join_delta_home_impl(e, state, state_ctx, nullptr, nullptr, nullptr, 0, spare, tree, home, swapped, true,
+                              &mu);
 }
 
 static int join_delta_impl(dg_engine* e, dg_store* state, dg_context* state_ctx, const dg_store* delta,

@@ -196,12 +196,14 @@ inline KdScratch kd_layout(Arena& a, uint64_t nk, uint64_t part_words, uint64_t 
   return s;
 }
 
-// dg_join_delta_home (engine sml): the edit | the per-key index (and a sixth, unused array
-// that keeps the offsets behind it) | the per-tile entry ranges | the moved word | the
-// result block
+// dg_join_delta_home (engine sml): the edit | the per-key index | a sixth array of its size:
+// dg_mutate_home's touched keys (nk = its ops: at most as many keys), which the kernel
+// writes and the splice after the wait reads; the join has its keyset from the caller and
+// leaves it unused | the per-tile entry ranges | the moved word | the result block
 struct HomeScratch {
   dg_store ed;
   KeyIndex idx;
+  uint64_t* keys;
   uint64_t* tile_u0;
   uint32_t* moved;
   uint64_t* res;
@@ -211,7 +213,7 @@ inline HomeScratch home_layout(Arena& a, uint64_t edit_rows, uint64_t nk, uint64
   HomeScratch s;
   s.ed = a.store(edit_rows);
   s.idx = key_index(a, nk);
-  a.take<uint64_t>(nk + 1);
+  s.keys = a.take<uint64_t>(nk + 1);
   s.tile_u0 = a.take<uint64_t>(a_tiles + 2);
   s.moved = a.take<uint32_t>(1);
   s.res = a.take<uint64_t>(result_words);

@@ -547,6 +547,17 @@ struct SmallArgs {
   RowsOut sp;          // the spare store (the rows moved: the output)
   u64* end;            // scratch: nk, each key's state rows' end
   i64* shift;          // scratch: nk + 1, the shift of the gap before each key (and after all)
+  // dg_mutate_home (launch_small_mutate; unused by the join, and behind its fields): m ops of
+  // `node` sorted by key, batch order within a key (dg_mutate_batch's arrays, device or page-
+  // locked host memory), instead of d, cd, keys and nk, which the kernel builds from them
+  const uint8_t* m_kind;  // 1 add, 0 remove
+  const u64 *m_key, *m_val;
+  const i64* m_ts;
+  const u64* m_rank;   // an add's rank among the batch's adds
+  u64 m, n_adds;
+  u32 node;
+  u64 sp_cap;          // the spare store's capacity: state rows + touched keys must fit
+  u64* keys_out;       // scratch (device): m, the touched keys ascending
 };
 // result block words: header [0] flags [1] changed keys [2] their rows [3] context entries
 // [4] edit rows [5] taken rows [6] moved [7] distinct-key change; then the changed keys
@@ -563,8 +574,14 @@ constexpr u64 SMALL_O_DOLD = SMALL_WORDS, SMALL_O_DNEW = SMALL_O_DOLD + SMALL_KE
 constexpr u64 SMALL_O_DFLAGS = SMALL_O_DNEW + SMALL_KEYS, SMALL_DIFFS_WORDS = SMALL_O_DFLAGS + SMALL_KEYS / 8;
 
 constexpr u32 SMALL_FALLBACK = 1u;  // flags: nothing written, the general path runs
+constexpr u32 SMALL_ORDER = 8u;     // (the mutation form) ops not sorted by key: nothing written
+// (the mutation form) the publish block's free word between the sequence number and the hop's
+// header: the touched keys' number, which sizes the splice after the wait
+constexpr int SMALL_PUB_TOUCHED = 17;
 // small_delta_kernel<diffs> (diffs: home has SMALL_DIFFS_WORDS)
 hipError_t launch_small_delta(const SmallArgs& p, bool diffs, hipStream_t st);
+// small_delta_kernel<diffs, true>: the same join of the delta that p.m ops of p.node make
+hipError_t launch_small_mutate(const SmallArgs& p, bool diffs, hipStream_t st);
 // small.hip: the moved rows' splice copy behind the small join, one launch: blocks
 // [0, tiles) copy the state's rows outside the keyset into the spare store (when the join
 // moved rows: res[6], res[0] == 0; the small join placed the edit's rows), and the last

@@ -201,8 +201,9 @@ __device__ __forceinline__ u32 delta_bound(const SmallLds& s, u32 nd, u64 k, boo
 }
 
 // The per-key merge of step 3: calls emit(row) for every kept row in order; returns
-// (kept rows, changed)
-template <class F>
+// (kept rows, changed).  MUT (the mutation form): the delta's context covers every state row --
+// it holds the touched keys' state dots by construction -- so no dot list is searched
+template <bool MUT = false, class F>
 __device__ __forceinline__ u32 merge_key(const SmallLds& s, u32 ia, u32 ie, u32 ja, u32 je, bool dvv, u32 ncd,
                                          bool* changed, F emit) {
   u32 ne = 0;
@@ -225,15 +226,15 @@ __device__ __forceinline__ u32 merge_key(const SmallLds& s, u32 ia, u32 ie, u32 
       ja++;
     } else if (c < 0) {  // the state's only: kept unless the delta's context covers it
       const Row r = lds_a(s, ia++);
-      if (!delta_covers(s, dvv, ncd, r.node, r.cnt)) {
+      if (!(MUT || delta_covers(s, dvv, ncd, r.node, r.cnt))) {
         emit(r);
         ne++;
       } else {
         chg = true;
       }
-    } else {  // the delta's only: kept unless the state's VV covers it
+    } else {  // the delta's only: kept unless the state's VV covers it (MUT: it covers no new dot)
       const Row r = lds_d(s, ja++);
-      if (!vv_tab_covers(s.tabS, r.node, r.cnt)) {
+      if (MUT || !vv_tab_covers(s.tabS, r.node, r.cnt)) {
         emit(r);
         ne++;
         chg = true;
@@ -427,14 +428,22 @@ __device__ __forceinline__ void tree_paths(const SmallArgs& p, SmallLds& s, bool
 // instruction: the kernel itself is the template (a body inlined into two wrappers is
 // compiled differently), and both instantiations use ONE LDS block at namespace scope (a
 // block per instantiation moves the plain kernel's register allocation).
+//
+// MUT (dg_mutate_home[_diffs]): the keys and the delta are not inputs but built here, in step
+// 1, from m <= SMALL_KEYS ops of one node (mutate.hip's rule): a touched key per key group, a
+// delta row for a group whose last op is an add, with dot (node, C[node] + 1 + add_rank).  The
+// delta's context is never listed: it covers every taken row (merge_key<true>), and its fold
+// into the union context is the taken rows' dots and C[node] + n_adds (LDS 64-bit max).  Every
+// MUT statement is under `if constexpr`: the two join instantiations compile as before.
 __shared__ SmallLds g_small_lds;
-template <bool DIFFS>
+template <bool DIFFS, bool MUT>
 __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   SSTAMP(0);
   SmallLds& s = g_small_lds;
   const int tid = threadIdx.x;
-  const u32 nk = (u32)p.nk, nd = (u32)p.d.n, ncd = (u32)p.cd.n, ncs = (u32)p.ca.n;
-  const bool dvv = p.cd.kind == 0;
+  u32 nk = MUT ? 0u : (u32)p.nk, nd = MUT ? 0u : (u32)p.d.n;  // (MUT: counted in step 1)
+  const u32 ncd = MUT ? 0u : (u32)p.cd.n, ncs = (u32)p.ca.n;
+  const bool dvv = !MUT && p.cd.kind == 0;
   if (tid == 0) {
     s.flags = 0;
     s.moved = 0;
@@ -451,6 +460,19 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   //      the threads from the bottom, so a one-key op's loads are in flight together
   u32 fl = 0;
   auto from_top = [&](u32 o) { return (u32)((2 * NT - 1 - tid - o) % NT); };
+  // (MUT) op `tid`, loaded where it lies (device or page-locked host memory)
+  u64 okey = 0, oval = 0, orank = 0;
+  i64 ots = 0;
+  u32 okind = 0;
+  if constexpr (MUT) {
+    if ((u32)tid < (u32)p.m) {
+      okey = p.m_key[tid];
+      oval = p.m_val[tid];
+      ots = p.m_ts[tid];
+      okind = p.m_kind[tid];
+      orank = p.m_rank[tid];
+    }
+  }
   for (u32 i = from_top(0); i < nd; i += NT) {
     s.dk[i] = p.d.key[i];
     s.dv[i] = p.d.val[i];
@@ -477,11 +499,46 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
       s.cd.dots.c[i] = c;
     }
   }
+  if constexpr (MUT) {
+    // the key groups: a group's head names a touched key, its last op decides the delta row.
+    // Neighbours are compared in LDS (dk), which the delta rows then overwrite: every read is
+    // before the scan's barrier, every write behind it
+    const u32 m = (u32)p.m, mnode = p.node & (SV - 1);
+    if (p.node >= SV) fl |= SMALL_FALLBACK;
+    const bool in = (u32)tid < m;
+    if (in) s.dk[tid] = okey;
+    __syncthreads();  // (and tabS)
+    const bool head = in && (tid == 0 || s.dk[tid - 1] != okey);
+    const bool last = in && ((u32)tid == m - 1 || s.dk[tid + 1] != okey);
+    if (in && tid > 0 && s.dk[tid - 1] > okey) fl |= SMALL_ORDER;
+    const bool row = last && okind != 0;
+    const u32 v[4] = {head ? 1u : 0u, row ? 1u : 0u, 0u, 0u};
+    u32 ex[4], tt[4];
+    block_scan4(v, s.w4, ex, tt);
+    nk = __builtin_amdgcn_readfirstlane(tt[0]);
+    nd = __builtin_amdgcn_readfirstlane(tt[1]);
+    if (head) {
+      s.key[ex[0]] = okey;
+      p.keys_out[ex[0]] = okey;  // (scratch, not the state: the splice after the wait reads the keys there)
+    }
+    if (row) {
+      const u32 j = ex[1];
+      s.dk[j] = okey;
+      s.dv[j] = oval;
+      s.dt[j] = ots;
+      s.dn[j] = p.node;
+      const u64 t1 = s.tabS[mnode];             // C[node] + 1, or 0: absent (compared as
+      s.dc[j] = (t1 ? t1 : 1ull) + orank;       // integers: max() of u64 and 1ull goes through double)
+    }
+    if (p.a.n + nk > p.sp_cap) fl |= SMALL_FALLBACK;  // a row per touched key may come
+    __syncthreads();  // (s.key)
+  }
+  auto key_of = [&](u32 u) { return MUT ? s.key[u] : p.keys[u]; };
   // (has_tree) the key's bucket node and row count, loaded with the search
   u64 t_old = 0;
   u32 t_cnt = 0;
   if ((u32)tid < nk && p.has_tree) {
-    const u64 b = bucket_of(p.t, p.keys[tid]);
+    const u64 b = bucket_of(p.t, key_of(tid));
     t_old = p.t.nodes[((1ull << p.t.depth) - 1) + b];
     t_cnt = p.t.counts[b];
   }
@@ -489,7 +546,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   const bool one_path = nk == 1 && p.has_tree;  // (uniform)
   u64 psib[TMAXD];
   if (one_path && tid < WAVE) {
-    const u64 b = bucket_of(p.t, p.keys[0]);
+    const u64 b = bucket_of(p.t, key_of(0));
 #pragma unroll
     for (int l = 0; l < TMAXD; l++) psib[l] = p.t.nodes[sib_at(p.t.depth, b, l)];
   }
@@ -497,7 +554,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   if (nk <= (u32)(NT / WAVE)) {  // (uniform) a few keys: one wave searches each
     const u32 u = (u32)tid / WAVE;
     if (u < nk) {
-      const u64 k = p.keys[u];
+      const u64 k = key_of(u);
       u64 lo;
       u32 run;
       wave_find(p.a.key, p.a.n, k, lo, run);
@@ -508,7 +565,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
       }
     }
   } else if ((u32)tid < nk) {
-    const u64 k = p.keys[tid];
+    const u64 k = key_of(tid);
     u64 lo;
     u32 run;
     key_run<SA>(p.a.key, p.a.n, k, lo, run);  // (dg_device.h: 4 rows per round trip)
@@ -538,8 +595,20 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     for (u32 i = tid; i < ncd; i += NT)
       if (s.cd.dots.n[i] < SV)
         atomicMax((unsigned long long*)&s.tabU[s.cd.dots.n[i]], (unsigned long long)(s.cd.dots.c[i] + 1));
+  if constexpr (MUT) {  // the adds' dots (node, C + 1 + r), r < n_adds: their max, as counter + 1
+    if (tid == 0 && p.n_adds) {
+      const u32 x = p.node & (SV - 1);
+      const u64 t1 = s.tabS[x], c1 = t1 ? t1 : 1ull, v = c1 + p.n_adds;
+      if (v < c1)  // C[node] + n_adds reaches 2^64 - 1
+        atomicOr(&s.flags, SMALL_FALLBACK);
+      else
+        atomicMax((unsigned long long*)&s.tabU[x], (unsigned long long)v);
+    }
+  }
   __syncthreads();
-  if (!(s.flags & SMALL_FALLBACK)) {
+  // (MUT) ops out of key order are a fallback to every later step: nothing runs on them
+  constexpr u32 STOP = MUT ? SMALL_FALLBACK | SMALL_ORDER : SMALL_FALLBACK;
+  if (!(s.flags & STOP)) {
     for (u32 q = tid; q < n_ak; q += NT) {
       u32 lo = 0, hi = nk;  // the last key u with aoff[u] <= q
       while (hi - lo > 1) {
@@ -555,8 +624,17 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
       s.at[q] = p.a.ts[g];
       s.an[q] = p.a.node[g];
       s.ac[q] = p.a.cnt[g];
+      if constexpr (MUT) {  // a taken row's dot is a dot of the delta's context
+        const u32 n = s.an[q];
+        const u64 c = s.ac[q];
+        if (n >= SV || c == ~0ull)
+          atomicOr(&s.flags, SMALL_FALLBACK);
+        else
+          atomicMax((unsigned long long*)&s.tabU[n], (unsigned long long)(c + 1));
+      }
     }
-    for (u32 i = tid; i < nd; i += NT) {
+    // (MUT: every delta key is a touched key by construction)
+    for (u32 i = tid; !MUT && i < nd; i += NT) {
       if (i > 0 && s.dk[i] == s.dk[i - 1]) continue;
       u32 lo = 0, hi = nk;
       while (lo < hi) {
@@ -571,7 +649,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
   }
   __syncthreads();
   SSTAMP(2);
-  const bool fallback = s.flags & SMALL_FALLBACK;  // (uniform)
+  const bool fallback = s.flags & STOP;  // (uniform)
   // ---- 3. the join per key: kept rows, changed, distinct-key change
   u32 ne = 0, chg = 0, ja = 0, je = 0;
   u64 ov = 0, nv = 0;  // (DIFFS) the winning value ids before and after
@@ -582,7 +660,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     bool c;
     i64 nts = 0;
     u32 nj = 0;
-    ne = merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
+    ne = merge_key<MUT>(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
       if constexpr (DIFFS) {  // (selects, not branches: nj == 0 is "no row so far")
         const bool w = (nj == 0) | (r.ts > nts);
         nts = w ? r.ts : nts;
@@ -638,7 +716,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     u64 h = 0;
     for (u32 i = s.aoff[tid]; i < s.aoff[tid + 1]; i++) h -= rh_row(p.t.th, lds_a(s, i));
     bool c;
-    merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c,
+    merge_key<MUT>(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c,
               [&](const Row& r) { h += rh_row(p.t.th, r); });
     s.leaf[tid] = h;
   }
@@ -675,6 +753,8 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     return;
   }
   // ---- 6. writes
+  if constexpr (MUT)
+    if (tid == 0) p.h_pub[SMALL_PUB_TOUCHED] = nk;  // (host memory: fenced by the publish)
   u64 t_new = 0;
   int t_drows = 0;
   bool t_dirty = false;  // a head thread whose bucket changed: t_new, its rows' change
@@ -687,7 +767,7 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
     bool c;
     u64* rk = home + SMALL_O_ROWS;
     const RowsOut rr{rk, rk + SE, (i64*)(rk + 2 * SE), (u32*)(rk + 4 * SE), rk + 3 * SE};
-    merge_key(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
+    merge_key<MUT>(s, s.aoff[tid], s.aoff[tid + 1], ja, je, dvv, ncd, &c, [&](const Row& r) {
       if (!moved)
         store_row(p.aw, a0 + j, r);  // in place: every key keeps its row count
       else if (p.splice_here)
@@ -739,6 +819,12 @@ __global__ __launch_bounds__(NT) void small_delta_kernel(SmallArgs p) {
           if (drows) t.counts[b] = (uint16_t)((i64)t_cnt + drows);
         }
       }
+    }
+  }
+  if constexpr (MUT) {  // the tail kernel's index has an entry per op: those past the touched keys end nowhere
+    if (moved && p.splice_here && (u32)tid >= nk && (u32)tid < (u32)p.m) {
+      p.end[tid] = ~0ull;
+      p.a_lo[tid] = ~0ull;
     }
   }
   // the union context: into the state's and the result block
@@ -897,9 +983,17 @@ namespace dg {
 
 hipError_t launch_small_delta(const SmallArgs& p, bool diffs, hipStream_t st) {
   if (diffs)
-    hipLaunchKernelGGL(small_delta_kernel<true>, dim3(1), dim3(NT), 0, st, p);
+    hipLaunchKernelGGL((small_delta_kernel<true, false>), dim3(1), dim3(NT), 0, st, p);
   else
-    hipLaunchKernelGGL(small_delta_kernel<false>, dim3(1), dim3(NT), 0, st, p);
+    hipLaunchKernelGGL((small_delta_kernel<false, false>), dim3(1), dim3(NT), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_small_mutate(const SmallArgs& p, bool diffs, hipStream_t st) {
+  if (diffs)
+    hipLaunchKernelGGL((small_delta_kernel<true, true>), dim3(1), dim3(NT), 0, st, p);
+  else
+    hipLaunchKernelGGL((small_delta_kernel<false, true>), dim3(1), dim3(NT), 0, st, p);
   return hipGetLastError();
 }
 

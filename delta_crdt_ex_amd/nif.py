@@ -99,6 +99,7 @@ _SIGS = {
     "dgr_engine_close": (I32, [VP]),
     "dgr_live_states": (U64, [VP]),
     "dgr_deltas_route_stats": (I32, [VP, PU64]),
+    "dgr_mutate_route_stats": (I32, [VP, PU64]),
     "dgr_dg": (VP, [VP]),
     "dgr_refresh_terms": (I32, [VP, VP, U64, VP, VP, U64]),
     "dgr_remap": (I32, [VP, VP, VP, U64]),
@@ -127,6 +128,8 @@ _SIGS = {
     "dgr_take": (I32, [VP, U64, VP, U64, C.POINTER(dg_store)]),
     "dgr_take_batch": (I32, [VP, U64, I32, C.POINTER(VP), PU64, C.POINTER(dgr_taken)]),
     # (its packing alone, host code: c_src/test_takes.c checks it)
+    "dgr_mutate_words": (U64, [U64]),
+    "dgr_mutate_pack": (I32, [PU64, U64, VP, PU64, PU64, VP, PU64]),
     "dgr_takes_words": (U64, [I32, PU64]),
     "dgr_takes_pack": (U64, [VP, VP, I32, C.POINTER(VP), PU64, C.POINTER(VP), PU64]),
     "dgr_merkle_build": (I32, [VP, U64, C.c_uint32]),
@@ -241,6 +244,16 @@ class Engine:
         rc = self.lib.dgr_deltas_route_stats(self.ptr, out)
         if rc:
             raise _abi.DeltaGpuError(rc, "dgr_deltas_route_stats failed")
+        return tuple(int(x) for x in out)
+
+    def mutate_route_stats(self):
+        """(tried, served, declined): how often this engine's mutate_batch[_diffs] tried
+        dg_mutate_home, was served by it and was declined (dgr_mutate_route_stats; the route is
+        DGR_MUTATE_ROUTE at engine open).  Not a NIF function: tests and A/B."""
+        out = (C.c_uint64 * 3)()
+        rc = self.lib.dgr_mutate_route_stats(self.ptr, out)
+        if rc:
+            raise _abi.DeltaGpuError(rc, "dgr_mutate_route_stats failed")
         return tuple(int(x) for x in out)
 
     def close(self):

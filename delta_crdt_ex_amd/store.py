@@ -947,6 +947,10 @@ class Engine:
         f = self.lib.dg_join_delta_home_diffs if _diffs else self.lib.dg_join_delta_home
         check(f(self.h, C.byref(ss), C.byref(sc), C.byref(sd), C.byref(cd), kp, nk, C.byref(sp), _ref(t),
                 self._home, C.byref(sw)))
+        return self._home_result(h, state, state_ctx, spare, tree, ss, sc, t, sw)
+
+    def _home_result(self, h, state, state_ctx, spare, tree, ss, sc, t, sw):
+        """What join_delta_home and mutate_home return from the result block, and the commit."""
         if int(h[0]) & _abi.DG_HOME_FALLBACK:
             return None
         nch, nr, nc = int(h[1]), int(h[2]), int(h[3])
@@ -968,13 +972,42 @@ class Engine:
         None when the library declined, else join_delta_home's tuple followed by (old_val,
         new_val, flags): value ids (0 where the flag is clear) and DG_DIFF_OLD | DG_DIFF_NEW
         bits, entry i describing changed key i."""
-        r = self.join_delta_home(state, state_ctx, delta, delta_ctx, keys, spare, tree, _diffs=True)
+        return self._home_diffs(self.join_delta_home(state, state_ctx, delta, delta_ctx, keys, spare, tree,
+                                                     _diffs=True))
+
+    def _home_diffs(self, r):
         if r is None:
             return None
         h, n = self.home_block(), len(r[0])
         fl = h[_abi.DG_HOME_DIFF_FLAGS:_abi.DG_HOME_DIFFS_WORDS].view(np.uint8)[:n].copy()
         return r + ((h[_abi.DG_HOME_DIFF_OLD:_abi.DG_HOME_DIFF_OLD + n].copy(),
                      h[_abi.DG_HOME_DIFF_NEW:_abi.DG_HOME_DIFF_NEW + n].copy(), fl),)
+
+    def mutate_home(self, state: Store, ctx: Context, node: int, kind: torch.Tensor, key: torch.Tensor,
+                    val: torch.Tensor, ts: torch.Tensor, add_rank: torch.Tensor, n_adds: int, spare: Store,
+                    tree: MerkleTree | None = None, _diffs: bool = False):
+        """dg_mutate_home: mutate_batch's ops (the same arrays) applied to the resident state in
+        one launch and one wait -- mutate_batch followed by join_delta_home with the touched
+        keys, without the delta or its dot list ever being made.  Returns what join_delta_home
+        returns; None when the library declined (nothing happened: run the two calls)."""
+        self._order()
+        h = self.home_block()
+        m = int(key.numel())
+        ss, sc, sp = state.abi(), ctx.abi(), spare.abi()
+        t = tree.abi() if tree is not None else None
+        sw = C.c_int(0)
+        f = self.lib.dg_mutate_home_diffs if _diffs else self.lib.dg_mutate_home
+        check(f(self.h, C.byref(ss), C.byref(sc), node, m, _ptr(kind, C.c_void_p) if m else None,
+                _ptr(key, _abi.P64), _ptr(val, _abi.P64), _ptr(ts, _abi.PI64), _ptr(add_rank, _abi.P64), n_adds,
+                C.byref(sp), _ref(t), self._home, C.byref(sw)))
+        return self._home_result(h, state, ctx, spare, tree, ss, sc, t, sw)
+
+    def mutate_home_diffs(self, state: Store, ctx: Context, node: int, kind: torch.Tensor, key: torch.Tensor,
+                          val: torch.Tensor, ts: torch.Tensor, add_rank: torch.Tensor, n_adds: int,
+                          spare: Store, tree: MerkleTree | None = None):
+        """dg_mutate_home_diffs: mutate_home with join_delta_home_diffs' (old_val, new_val, flags)."""
+        return self._home_diffs(self.mutate_home(state, ctx, node, kind, key, val, ts, add_rank, n_adds, spare,
+                                                 tree, _diffs=True))
 
     def merkle_update(self, tree: MerkleTree, new: Store, keys: torch.Tensor) -> MerkleTree:
         """MerkleMap.put/delete of the changed `keys` + update_hashes: `tree` indexed

@@ -578,6 +578,29 @@ int dg_mutate_batch_async(dg_engine* e, const dg_store* state, const dg_context*
                           dg_context* delta_dots, uint64_t* keys_out, uint64_t keys_cap,
                           uint64_t* n_keys_out);
 
+/* dg_mutate_batch followed by dg_join_delta_home with the touched keys as keyset, in ONE
+ * launch and ONE host wait: the ops (dg_mutate_batch's arrays, in device memory or memory from
+ * dg_host_alloc, which the kernel reads in place) are applied to the resident replica -- the
+ * delta is built and joined inside the one-workgroup join, and its dot list is never made.
+ * On return the state, its context, the tree and `home` (dg_join_delta_home's block and
+ * header words) are bit for bit what the two calls give; *swapped, the all-or-nothing rule
+ * and the tree's input errors are dg_join_delta_home's.  Ops not sorted by key: DG_E_ORDER,
+ * nothing touched.  Served: m <= 512; state_ctx a version vector of <= DG_HOME_NODES entries
+ * with state_ctx->cap >= state_ctx->n + 1; every node id (the context's, the touched keys'
+ * state rows', `node`) < DG_HOME_NODES; <= 1024 state rows under the touched keys; no counter
+ * at 2^64 - 1 and C[node] + n_adds below it; spare->cap >= state->n + touched keys; store
+ * columns 16-byte aligned.  The number of dots is not limited.  Otherwise home[0] =
+ * DG_HOME_FALLBACK, nothing is touched and DG_OK is returned: the caller runs the two calls. */
+int dg_mutate_home(dg_engine* e, dg_store* state, dg_context* state_ctx, uint32_t node, uint64_t m,
+                   const uint8_t* kind, const uint64_t* key, const uint64_t* val, const int64_t* ts,
+                   const uint64_t* add_rank, uint64_t n_adds, dg_store* spare, dg_merkle* tree,
+                   uint64_t* home, int* swapped);
+/* ... with dg_join_delta_home_diffs' three ranges: `home` has DG_HOME_DIFFS_WORDS words */
+int dg_mutate_home_diffs(dg_engine* e, dg_store* state, dg_context* state_ctx, uint32_t node, uint64_t m,
+                         const uint8_t* kind, const uint64_t* key, const uint64_t* val, const int64_t* ts,
+                         const uint64_t* add_rank, uint64_t n_adds, dg_store* spare, dg_merkle* tree,
+                         uint64_t* home, int* swapped);
+
 /* ---- causal-context algebra ----------------------------------------------- */
 /* Dots.union/2 (aw_lww_map.ex:39-52): VV ⊔ VV = per-node max; VV ⊔ DOTS folds the
  * dots into the VV; DOTS ⊔ DOTS = set union. */
