@@ -20,6 +20,12 @@
 // one-workgroup scan, write (keys, rows, the state dots), generate the adds' dots, then
 // two stable radix sorts (rocPRIM: by counter, then by node) give the (node, counter)
 // order of a dot list.
+//
+// The list has n_state_dots + n_adds entries, a count fixed before any dot is looked at, and
+// is sorted, not deduplicated.  A touched key's state row that already carries a dot (i, C[i]
+// + 1 + r), r < n_adds -- a state whose context does not cover its rows' dots -- is therefore
+// listed twice, where the oracle's set lists it once.  The joins search or compress the
+// list, so the joined state is the same (tests/test_gpu_mutate_seams.py, own_dot).
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "dg_launch.h"

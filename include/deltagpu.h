@@ -557,8 +557,12 @@ int dg_replace_keysets(dg_engine* e, dg_store* state, uint64_t k, const uint64_t
  *   delta      one row per touched key whose last op is an add, with dot
  *              {node, C[node] + 1 + add_rank} (C = ctx, a version vector);
  *   delta_dots the delta's context as a sorted dot list: the dots of the touched keys'
- *              rows in `state` plus the dot of every add;
- *   keys_out   the touched keys, ascending, *n_keys_out of them (cap keys_cap).
+ *              rows in `state` plus the dot of every add.  The list is sorted, not
+ *              deduplicated, and delta_dots->n is always those two counts added: a touched
+ *              key's state row that already carries a dot {node, C[node] + 1 + r}, r <
+ *              n_adds (a state whose context does not cover its rows) is listed twice.
+ *              The joins search or compress the list, so the joined state is the same;
+ *   keys_out  the touched keys, ascending, *n_keys_out of them (cap keys_cap).
  * dg_join2(state, ctx, delta, delta_dots, keys_out, ...) then equals applying the ops
  * one by one.  Capacities: delta->cap >= touched keys, delta_dots->cap >= touched
  * keys' rows + n_adds (DG_E_CAPACITY names the sizes).  Synchronous. */

@@ -4,7 +4,9 @@ the join when it declines; =batch is that sequence alone.  A history of one-key 
 batch and a 600-op batch (over the home call's 512: not tried) run through nif.py under each
 route on an engine of its own, on a state with a tree: both routes return the same changed
 keys, diffs, context and version steps and leave the same rows, reads and tree, and the
-engine's counters (dgr_mutate_route_stats) say which route ran.  And
+engine's counters (dgr_mutate_route_stats) say which route ran.  Removes of keys with more
+rows than the first dot capacity allows take the copy route's second attempt and give what
+one-op calls give.  And
 causal_crdt.update_resident_state_with_ops against apply_ops on a non-resident twin."""
 import os
 
@@ -92,6 +94,56 @@ def test_both_routes_give_the_same():
     assert [x[1] for x in oh] == [(i + 1, i + 1, 0) for i in range(n - 1)] + [(n - 1, n - 1, 0)]
     assert all(x[1] == (0, 0, 0) for x in ob)
     assert oh[-2][1][1] > 0
+
+
+def _removes(name, base, keys, slice_len, diffs):
+    """`keys` of `base` removed under route `name`, slice_len ops to a call: (changed keys and
+    diffs of all calls, the final reads, rows and tree, the route's counters)"""
+    ops = [("remove", tg(k)) for k in keys]
+    changed, dd = [], []
+    with route(name) as node:
+        res, ver = _twin(base)
+        f = nif.mutate_batch_diffs if diffs else nif.mutate_batch
+        for i in range(0, len(ops), slice_len):
+            r = f(res, ver, tg("n2"), ops[i:i + slice_len])
+            assert r[0] == "ok" and r[1] == ver + 1, r
+            ver = r[1]
+            changed += r[3]
+            dd += r[4] if diffs else []
+        stats = node.stats()
+        final = (nif.read(res, ver, "all"), nif.take(res, ver, [tg(k) for k in keys]),
+                 nif.merkle_prepare(res, ver, B.LEVELS))
+    return sorted(changed, key=repr), sorted(dd, key=repr), final, stats
+
+
+def test_more_state_dots_than_the_first_dot_capacity():
+    """dgr_mutate_batch asks dg_mutate_batch_async for 8m + n_adds + 1 context dots and, on
+    DG_E_CAPACITY, once more for state rows + n_adds + 1.  Removes of keys with more than 8 rows
+    each need the second: one 12-row key (12 > 9; and one 26-row key, past the 16 entries of
+    slack the buffer's first allocation adds) under `batch`, and 600 keys of 9 rows (5,400 >
+    4,801; over the home call's 512 ops, so not tried) under both routes.  The same changed
+    keys, diffs, reads, rows and tree as a twin that takes the ops one to a call (9 <= 8 + 1:
+    no retry), and the counters say which route ran."""
+    for n_nodes in (12, 26):
+        base = _peer(list(range(1, n_nodes + 1)), list(range(8)), lambda j, i: ("v", j, i), 100)
+        assert all(len(v) == n_nodes for v in base.value.values()) and n_nodes > 8 * 1 + 0 + 1
+        one = _removes("batch", base, [3], 1, True)
+        twin = _removes("home", base, [3], 1, True)  # (dg_mutate_home: no dot list to size)
+        assert one[:3] == twin[:3] and len(one[0]) == 1 and one[1] == [("remove", tg(3))]
+        assert one[3] == (0, 0, 0) and twin[3] == (1, 1, 0)
+    base = _peer(list(range(1, 10)), list(range(600)), lambda j, i: ("v", j, i), 100)
+    assert all(len(v) == 9 for v in base.value.values()) and 600 * 9 > 8 * 600 + 0 + 1 + 16
+    keys = [(i * 7) % 600 for i in range(600)]  # (batch order is not key order)
+    for name in ROUTES:
+        one = _removes(name, base, keys, 600, True)
+        twin = _removes(name, base, keys, 1, True)
+        assert one[:3] == twin[:3]
+        assert len(one[0]) == 600 and all(v is None for _, v in one[0]) and len(one[1]) == 600
+        assert one[2][0] == ("ok", {})
+        assert one[3] == (0, 0, 0)
+        assert twin[3] == ((600, 600, 0) if name == "home" else (0, 0, 0))
+    plain = _removes("batch", base, keys, 600, False)
+    assert plain[0] == one[0] and plain[2] == one[2]
 
 
 def test_update_resident_state_with_ops_equals_apply_ops():
