@@ -130,6 +130,52 @@ __device__ __forceinline__ bool fill_vv_tables(const Ctx& ca, const Ctx& cb, u64
   return far;
 }
 
+// The fused stream kernel fills the tables off its serial path, when neither VV has more
+// than a wave's worth of entries (VVs whose node ids all lie below VT): every lane loads
+// entry `lane` of both VVs at kernel entry (issue_vv), AHEAD of the first tile's loads, so
+// the wait for them is a counted vmcnt that leaves the tile's loads in flight; wave 0 then
+// zeroes and fills both tables by itself (fill_vv_wave0: one wave's LDS writes land in
+// program order, so no barrier stands between the zeroes and the entries) while the tile
+// streams in and the other waves check their splits, and the barrier behind the split
+// checks publishes them.  Not the keyed kernels: they sit at 128 VGPRs, and the staged
+// entries cost them scratch.
+static_assert(VT == WAVE, "fill_vv_wave0 zeroes one table entry per lane");
+struct VvStaged {  // one lane's entry of each VV, in registers
+  u32 an, bn;
+  u64 ac, bc;
+};
+
+__device__ __forceinline__ bool vv_in_wave(const Ctx& ca, const Ctx& cb) {
+  return (ca.n <= (u64)WAVE) & (cb.n <= (u64)WAVE);
+}
+
+// Branch-free: a lane without an entry loads entry 0, and from a store's key column when
+// the context is empty (its pointers may be null; a store with rows exists, slot_row).
+__device__ __forceinline__ void issue_vv(const Ctx& ca, const Ctx& cb, const Rows& A, const Rows& B,
+                                         VvStaged& v) {
+  const u64 lane = threadIdx.x & (WAVE - 1);
+  const u64* some = A.n ? A.key : B.key;
+  const u64 na = ca.n, nb = cb.n;
+  const u64 ia = lane < na ? lane : 0, ib = lane < nb ? lane : 0;
+  v.an = gload(na ? ca.node : (const u32*)some, ia);
+  v.ac = gload(na ? ca.cnt : some, ia);
+  v.bn = gload(nb ? cb.node : (const u32*)some, ib);
+  v.bc = gload(nb ? cb.cnt : some, ib);
+}
+
+// Wave 0 only, VVs of at most WAVE entries each.  Returns (wave-uniform) whether a VV has
+// an entry outside the tables.
+__device__ __forceinline__ bool fill_vv_wave0(const VvStaged& v, u64 na, u64 nb, u64* tab_a,
+                                              u64* tab_b) {
+  const u64 lane = threadIdx.x & (WAVE - 1);
+  tab_a[lane] = 0;
+  tab_b[lane] = 0;
+  const bool ha = lane < na, hb = lane < nb;
+  if (ha & (v.an < (u32)VT)) tab_a[v.an] = v.ac;
+  if (hb & (v.bn < (u32)VT)) tab_b[v.bn] = v.bc;
+  return __ballot((ha & (v.an >= (u32)VT)) | (hb & (v.bn >= (u32)VT))) != 0;
+}
+
 // ------------------------------------------------------------------- staging
 // One staged tile: its rows (+ one neighbour on each side of each store), as 16-byte
 // {key, val} and {ts, cnt} pairs plus the node column: a whole row is 3 LDS accesses

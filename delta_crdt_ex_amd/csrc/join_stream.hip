@@ -91,6 +91,7 @@ struct StreamLds {
   u64 spl[2 * FUSE_IT];  // fused: splits of this workgroup's tiles (start, end per tile)
   u64 chk[JB / WAVE];    // CHG: each wave's last change event, and 1 + its lane (0: none)
   int chf[JB / WAVE];
+  int vvfar;  // fused: whether a VV has an entry outside the tables (wave 0, fill_vv_wave0)
 };
 
 constexpr u32 CNT_BITS = 12;  // count field of a tile-count granule (JT < 4096)
@@ -240,16 +241,25 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   const Rows& A = p.a;
   const Rows& B = p.b;
   if (tid == 0)  // residency check (stripe_sums)
-    __hip_atomic_store(cold(&cold_scan()->started) + w, epoch, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p.scan.started + w, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (w < G) JSTAMP(w, 0);  // (stamps build: slot 0 of a workgroup's first tile = its entry)
   if (w < G) JSTAMP_PLACE(w);
   Staged r;
   u64 ga0 = 0, ga1 = 0;  // fused: the first tile's speculative splits
+  // fused, version vectors: the VV tables are filled beside the split checks (dg_jtile.h)
+  constexpr bool VV_EARLY = LATE && FAST && !KEYED;
+  VvStaged vr;
   if (LATE) {
     if (w == G) {  // Dots.union(c1, c2) (aw_lww_map.ex:155), beside the tiles
       ctx_union_block<JB>(p.cu, s.wave);
       return;
+    }
+    // The VVs' entries are loaded ahead of the first tile: loads return in order, so the
+    // wait for them is a counted one that leaves the tile's loads in flight.  (A scheduling
+    // barrier: the compiler's scheduler would move them behind the tile's.)
+    if (VV_EARLY) {
+      issue_vv(p.ca, p.cb, A, B, vr);
+      __builtin_amdgcn_sched_barrier(0);
     }
     // The first tile's loads go out at the proportional splits d * na / (na + nb) BEFORE
     // the exact search: replicas that hold the same keys (config 2) split exactly there,
@@ -262,14 +272,21 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       tile_geom(w, p.jt, ga0, ga1, total, &gnat, &gnbt, &gb0);
       issue_tile(A, B, gnat, ga0, gb0, r);
     }
+    // wave 0 writes the VV tables while the tile is in flight; the barrier behind the split
+    // checks publishes them
+    if (VV_EARLY && tid < WAVE && vv_in_wave(p.ca, p.cb)) {
+      const bool far = fill_vv_wave0(vr, p.ca.n, p.cb.n, s.tab[0], s.tab[1]);
+      if (tid == 0) s.vvfar = far;
+    }
     // merge-path splits of this workgroup's (<= FUSE_IT) tiles: boundary q (tile q / 2,
     // side q % 2) by wave q mod the block's waves
     for (int q = tid / WAVE; q < 2 * FUSE_IT; q += JB / WAVE) {  // (wave-uniform)
       const u64 tk = w + (u64)(q >> 1) * G;
       if (tk >= ntiles) break;
       const u64 d = min((tk + (q & 1)) * p.jt, total);
-      // the proportional split is checked first with scalar loads (a counter the tile
-      // loads in flight do not hold up); the search runs only where it is not exact
+      // the proportional split is checked first; the search runs only where it is not
+      // exact.  (The check's loads are vector loads, q not being uniform to the compiler:
+      // each waits for the tile's loads before it)
       const u64 g = split_guess(A.n, B.n, d);
       const u64 sp = guess_exact(A, B, d, g) ? g : mp_split(A, B, d);
       if ((tid & (WAVE - 1)) == 0) s.spl[q] = sp;
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       }
     }
   }
-  if (FAST)
+  if (FAST && !VV_EARLY)
     for (int x = tid; x < 2 * VT; x += JB) (&s.tab[0][0])[x] = 0;
   if (LATE) __syncthreads();
   if (w < G) JSTAMP(w, 8);  // (stamps build: splits searched)
@@ -330,10 +347,19 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     km = kslice(t, 0, &kl);
     if (km <= (u64)KS && (u64)tid < km) kk = p.keys[kl + tid];
   }
-  __syncthreads();  // zeroed tables visible
+  if (!VV_EARLY) __syncthreads();  // zeroed tables visible
   if (w < G) JSTAMP(w, 9);  // (stamps build: first tile's loads issued)
   bool vv_far = false;
-  if (FAST) {
+  if (VV_EARLY) {
+    if (vv_in_wave(p.ca, p.cb)) {  // (uniform) filled by wave 0, before the barrier above
+      vv_far = __builtin_amdgcn_readfirstlane(s.vvfar) != 0;
+    } else {  // a VV of more than VT entries has one outside the tables: the merge with the
+              // coverage search, and its tables filled as the partitioned kernel's are
+      for (int x = tid; x < 2 * VT; x += JB) (&s.tab[0][0])[x] = 0;
+      __syncthreads();
+      vv_far = __syncthreads_or(fill_vv_tables(p.ca, p.cb, s.tab[0], s.tab[1]));
+    }
+  } else if (FAST) {
     vv_far = fill_vv_tables(p.ca, p.cb, s.tab[0], s.tab[1]);  // once per workgroup
     if (LATE) vv_far = __syncthreads_or(vv_far);
   }
@@ -343,7 +369,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   // CUs: speed only, nothing depends on it).  A bounded sleep: it waits on nothing, and
   // behind a long one the lower half meets the wait for the stripe before (the tests).
   if (2 * w >= G)  // (the upper half: `upper` below)
-    for (int i = cold(&((const JoinArgs*)__builtin_amdgcn_kernarg_segment_ptr())->stagger); i > 0; i--)
+    for (int i = p.stagger; i > 0; i--)
       __builtin_amdgcn_s_sleep(STAGGER_SLEEP);
   u64 off = 0;  // output offset of this workgroup's previous tile (of tile w: the counts below it)
   u32 np = 0;    // kept rows of this workgroup's tile of the previous stripe
