@@ -41,6 +41,12 @@
  *                                                      -> {:ok, version', new_dots, changed, diffs}
  *        the pending {:diff, delta, keys} messages of the mailbox joined in one call
  *        (dg_join_deltas); changed and diffs are NET over the batch
+ *   sync_from(dst, dst_version, src, src_version, max)  -> {:ok, version', new_dots, changed, n_total}
+ *   sync_from_diffs(dst, dst_version, src, src_version, max)
+ *                                                      -> {:ok, version', new_dots, changed, n_total, diffs}
+ *        one anti-entropy exchange from `src` toward `dst`, two states of ONE engine, device to
+ *        device (dgr_sync_from: dg_merkle_diff_take, then the join of the rows where they
+ *        stand); n_total the untruncated number of differing keys
  *   read(state, version, keys | :all)                 -> {:ok, %{key => value}}  (:211-224)
  *   take(state, version, keys)                         -> {:ok, value map}  (Map.take, :118,331)
  *   take_batch(state, version, [keys, ...])            -> {:ok, [value map, ...]}  (k takes, one pass)
@@ -707,8 +713,16 @@ static int diffs_list(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const
 /* {:ok, version, new_dots, [{key, value_map | nil}]} from a join's result: the changed
  * keys' rows (in key order) walked into value maps, the context into its term; with `d`
  * {:ok, version, new_dots, changed, diffs} */
+static int changed_result_total(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const dgr_diffs* d,
+                                const uint64_t* n_total, ERL_NIF_TERM* r);
 static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const dgr_diffs* d,
                           ERL_NIF_TERM* r) {
+  return changed_result_total(env, g, c, d, NULL, r);
+}
+
+/* ... with n_total (sync_from): {:ok, version, new_dots, changed, n_total [, diffs]} */
+static int changed_result_total(ErlNifEnv* env, engine_res* g, const dgr_changed* c, const dgr_diffs* d,
+                                const uint64_t* n_total, ERL_NIF_TERM* r) {
   ERL_NIF_TERM values, dots, changed = enif_make_list(env, 0);
   int rc = unmarshal_host_rows(env, g, &c->rows, &values);
   if (!rc) rc = unmarshal_dots(env, g, &c->ctx, &dots);
@@ -723,10 +737,14 @@ static int changed_result(ErlNifEnv* env, engine_res* g, const dgr_changed* c, c
   if (d) {
     ERL_NIF_TERM diffs;
     if ((rc = diffs_list(env, g, c, d, &diffs))) return rc;
-    *r = enif_make_tuple5(env, A_OK, enif_make_uint64(env, c->version), dots, changed, diffs);
+    *r = n_total ? enif_make_tuple6(env, A_OK, enif_make_uint64(env, c->version), dots, changed,
+                                    enif_make_uint64(env, *n_total), diffs)
+                 : enif_make_tuple5(env, A_OK, enif_make_uint64(env, c->version), dots, changed, diffs);
     return DG_OK;
   }
-  *r = enif_make_tuple4(env, A_OK, enif_make_uint64(env, c->version), dots, changed);
+  *r = n_total ? enif_make_tuple5(env, A_OK, enif_make_uint64(env, c->version), dots, changed,
+                                  enif_make_uint64(env, *n_total))
+               : enif_make_tuple4(env, A_OK, enif_make_uint64(env, c->version), dots, changed);
   return DG_OK;
 }
 
@@ -777,6 +795,51 @@ static ERL_NIF_TERM join_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
 static ERL_NIF_TERM join_delta_diffs(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   (void)argc;
   return join_delta_impl(env, argv, 1);
+}
+
+/* sync_from(dst, dst_version, src, src_version, max_sync_size | :infinite)
+ *   -> {:ok, version', new_dots, changed, n_total}
+ * One anti-entropy exchange from `src` toward `dst`, two states of ONE engine, device to device
+ * (dgr_sync_from): the trees' diff answered with src's rows of the first max_sync_size differing
+ * keys, joined into dst where they stand -- no row becomes a term, none is interned again.
+ * n_total: the untruncated number of differing keys (another round while it exceeds
+ * max_sync_size).  The result marshals exactly as join_delta's; sync_from_diffs appends diffs. */
+static ERL_NIF_TERM sync_from_impl(ErlNifEnv* env, const ERL_NIF_TERM argv[], int with_diffs) {
+  state_res *s, *src;
+  uint64_t version, src_version, n_total = 0;
+  ErlNifUInt64 max_sync = 0; /* (dgr_sync_from: 0 is :infinite) */
+  if (!get_state(env, argv[0], argv[1], &s, &version) || !get_state(env, argv[2], argv[3], &src, &src_version) ||
+      (!enif_is_identical(argv[4], A_INFINITE) && (!enif_get_uint64(env, argv[4], &max_sync) || max_sync == 0)))
+    return enif_make_badarg(env);
+  engine_res* g = s->eng;
+  if (src->eng != g) return error_term(env, DG_E_INVAL); /* (one engine, one lock) */
+  enif_mutex_lock(g->lock);
+  int rc = DG_OK;
+  dgr_changed c;
+  ERL_NIF_TERM r = A_NIL;
+  if (dgr_state_has_tree(s->s) && dgr_state_has_tree(src->s)) TRY(refresh_terms(g));
+  if (with_diffs) {
+    dgr_diffs d;
+    TRY(dgr_sync_from_diffs(s->s, version, src->s, src_version, max_sync, &c, &d, &n_total));
+    TRY(changed_result_total(env, g, &c, &d, &n_total, &r));
+  } else {
+    TRY(dgr_sync_from(s->s, version, src->s, src_version, max_sync, &c, &n_total));
+    TRY(changed_result_total(env, g, &c, NULL, &n_total, &r));
+  }
+out:
+  if (rc) r = error_term(env, rc);
+  enif_mutex_unlock(g->lock);
+  return r;
+}
+
+static ERL_NIF_TERM sync_from_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return sync_from_impl(env, argv, 0);
+}
+
+static ERL_NIF_TERM sync_from_diffs_nif(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return sync_from_impl(env, argv, 1);
 }
 
 /* join_deltas(state, version, [{dots, value, keys}, ...]) -> {:ok, version', new_dots, changed}
@@ -1359,6 +1422,8 @@ static ErlNifFunc funcs[] = {
     {"join_delta", 5, join_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"mutate_batch", 4, mutate_batch_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"join_delta_diffs", 5, join_delta_diffs, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"sync_from", 5, sync_from_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"sync_from_diffs", 5, sync_from_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"mutate_batch_diffs", 4, mutate_batch_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"join_deltas", 3, join_deltas_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"join_deltas_diffs", 3, join_deltas_diffs_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},

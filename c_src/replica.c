@@ -139,6 +139,8 @@ int dgr_engine_close(dgr_engine* g) {
   dg_host_free(e, g->h_bstage);
   dg_host_free(e, g->h_tstage);
   dg_host_free(e, g->h_tfall);
+  dg_buffer_free(e, g->d_sy);
+  dg_store_free(e, &g->sy_rows);
   free(g->h_bin);
   free(g->sw_stores);
   free(g->b_rows); /* (and b_ctx, b_keys, b_nk, b_unsorted behind it) */

@@ -138,6 +138,25 @@ int dgr_mutate_batch_diffs(dgr_state* s, uint64_t version, uint32_t node, uint64
                            const uint64_t* key, const uint64_t* val, const int64_t* ts, dgr_changed* out,
                            dgr_diffs* diffs);
 
+/* One whole anti-entropy exchange originated by `src` toward `dst`, both resident on ONE engine
+ * (causal_crdt.ex:252-270, :91-123, :324-335, then :383-404 on the receiver), as one call and
+ * device to device: the two trees are diffed and src's rows of the first max_sync differing keys
+ * (ascending key id; 0: every key) come out of the same launch chain (dg_merkle_diff_take) into
+ * engine-owned device buffers, and are joined into dst where they stand, with src's context as
+ * the delta's and the kept keys as the keyset: join(dst, %{dots: src.dots, value:
+ * Map.take(src.value, keys)}, keys).  No row becomes a term and none is interned again.  The
+ * kept keys are dg_merkle_diff's truncation (the first max_sync by key id), not the hop
+ * protocol's.  out, diffs and dst's version step are dgr_join_delta[_diffs]'; src and its version
+ * are untouched; *n_total is the untruncated number of differing keys, and the caller runs
+ * another round while it exceeds max_sync.  No differing key: DG_OK, n_changed = 0, dst's version
+ * unchanged, no join launched.  Before any launch: DG_E_INVAL for a null argument, dst == src,
+ * states of different engines, a state without a tree, trees of different depth or shard;
+ * DGR_E_STALE for either version. */
+int dgr_sync_from(dgr_state* dst, uint64_t dst_version, dgr_state* src, uint64_t src_version,
+                  uint64_t max_sync /* 0: infinite */, dgr_changed* out, uint64_t* n_total);
+int dgr_sync_from_diffs(dgr_state* dst, uint64_t dst_version, dgr_state* src, uint64_t src_version,
+                        uint64_t max_sync, dgr_changed* out, dgr_diffs* diffs, uint64_t* n_total);
+
 /* update_state_with_delta for a BATCH of k deltas -- the {:diff, delta, keys} messages
  * pending in a replica's mailbox -- as one call: all k deltas, contexts and keysets (host,
  * any order, as for dgr_join_delta) go down as ONE packed message and one copy, deltas the

@@ -82,6 +82,11 @@ struct dgr_engine {
    * rp_take_carve), and those of the hops that took theirs through dgr_take_batch, per hop */
   uint64_t *h_tstage, *h_tfall;
   uint64_t h_tstage_cap, h_tfall_cap;
+  /* dgr_sync_from: the kept keys and their row offsets (device: keys [0, cap) | offs behind
+   * them), and the source's rows of those keys */
+  uint64_t* d_sy;
+  uint64_t sy_cap;
+  dg_store sy_rows;
   /* dgr_sweep: the live states' stores as one host array */
   dg_store* sw_stores;
   uint64_t sw_cap;

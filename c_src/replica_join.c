@@ -226,6 +226,53 @@ int dgr_join_delta_diffs(dgr_state* s, uint64_t version, const dg_store* delta, 
   return diffs ? join_delta(s, version, delta, delta_ctx, keys, n_keys, out, diffs) : DG_E_INVAL;
 }
 
+/* dgr_sync_from (diffs NULL) and dgr_sync_from_diffs: the diff of the two trees answered with
+ * src's rows of the kept keys (dg_merkle_diff_take, side 1: one launch chain, one wait) into
+ * engine-owned device buffers, then apply_delta with those rows where they stand, src's context
+ * as the delta's and the kept keys as the keyset.  Nothing goes through the host but counts. */
+static int sync_from(dgr_state* dst, uint64_t dst_version, dgr_state* src, uint64_t src_version, uint64_t max_sync,
+                     dgr_changed* out, dgr_diffs* diffs, uint64_t* n_total) {
+  if (!dst || !src || !out || !n_total || dst == src || dst->g != src->g) return DG_E_INVAL;
+  if (!dst->has_tree || !src->has_tree) return DG_E_INVAL;
+  if (dst->tree.depth != src->tree.depth || dst->tree.shard_bits != src->tree.shard_bits ||
+      dst->tree.shard != src->tree.shard)
+    return DG_E_INVAL;
+  TRY(check_version(dst, dst_version));
+  TRY(check_version(src, src_version));
+  dgr_engine* g = dst->g;
+  /* at most one differing key per distinct key of either state */
+  const uint64_t most = dst->tree.n_keys + src->tree.n_keys;
+  const uint64_t cap = umax(max_sync ? umin(max_sync, most) : most, 1);
+  TRY(ri_grow(g, NULL, &g->d_sy, &g->sy_cap, 2 * cap + 1)); /* keys [0, cap) | offs [cap, 2 cap + 1) */
+  TRY(ri_grow_store(g, &g->sy_rows, umax(umin(src->rows.n, 4 * cap + 64), 1)));
+  uint64_t n = 0;
+  int rc = dg_merkle_diff_take(g->e, &dst->tree, &dst->rows, &src->tree, &src->rows, 1, g->d_sy, cap, g->d_sy + cap,
+                               &g->sy_rows, &n, n_total);
+  if (rc == DG_E_CAPACITY) { /* a key with many entries: once more with the room the call asked for */
+    TRY(ri_grow_store(g, &g->sy_rows, g->sy_rows.n));
+    rc = dg_merkle_diff_take(g->e, &dst->tree, &dst->rows, &src->tree, &src->rows, 1, g->d_sy, cap, g->d_sy + cap,
+                             &g->sy_rows, &n, n_total);
+  }
+  TRY(rc);
+  if (n == 0) { /* nothing differs: the context comes home, the version stays, no join */
+    back_views v;
+    TRY(open_back(g, 64, dst->ctx.n, &v));
+    TRY(ctx_home(dst, &v.co));
+    return bring_home(dst, 0, &v, out, diffs);
+  }
+  return apply_delta(dst, &g->sy_rows, &src->ctx, g->d_sy, n, out, diffs, 1);
+}
+
+int dgr_sync_from(dgr_state* dst, uint64_t dst_version, dgr_state* src, uint64_t src_version, uint64_t max_sync,
+                  dgr_changed* out, uint64_t* n_total) {
+  return sync_from(dst, dst_version, src, src_version, max_sync, out, NULL, n_total);
+}
+
+int dgr_sync_from_diffs(dgr_state* dst, uint64_t dst_version, dgr_state* src, uint64_t src_version, uint64_t max_sync,
+                        dgr_changed* out, dgr_diffs* diffs, uint64_t* n_total) {
+  return diffs ? sync_from(dst, dst_version, src, src_version, max_sync, out, diffs, n_total) : DG_E_INVAL;
+}
+
 /* Which batches try dg_join_deltas_keyed first (g->deltas_route, DGR_DELTAS_ROUTE at engine
  * open): `keyed` every batch, `stream` none.  `auto` is to be the region where the keyed call
  * measures faster than both the streaming call and k single joins THROUGH THIS LAYER; that

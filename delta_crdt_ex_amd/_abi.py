@@ -304,6 +304,9 @@ _SIGS = {
     "dg_merkle_diff": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store),
                                  C.POINTER(dg_merkle), C.POINTER(dg_store), P64, C.c_uint64, P64,
                                  P64]),
+    "dg_merkle_diff_take": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store),
+                                      C.POINTER(dg_merkle), C.POINTER(dg_store), C.c_int, P64, C.c_uint64,
+                                      P64, C.POINTER(dg_store), P64, P64]),
     "dg_merkle_diff_async": (C.c_int, [C.c_void_p, C.POINTER(dg_merkle), C.POINTER(dg_store),
                                        C.POINTER(dg_merkle), C.POINTER(dg_store), P64, C.c_uint64,
                                        P64]),

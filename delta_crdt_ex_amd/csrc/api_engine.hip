@@ -359,7 +359,7 @@ int dg_engine_destroy(dg_engine* e) {
   hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
   for (Buf* b : {&e->state, &e->tmp, &e->counts, &e->fold, &e->spl, &e->ubuf, &e->sml, &e->kdb, &e->kdz, &e->rpl,
-                 &e->diff_bsum})
+                 &e->diff_bsum, &e->diff_rsum})
     if (b->p) hipFree(b->p);
   if (e->d_counts) hipFree(e->d_counts);
   if (e->h_counts) hipHostFree(e->h_counts);

@@ -105,6 +105,57 @@ int dg_merkle_diff(dg_engine* e, const dg_merkle* a, const dg_store* sa, const d
   return DG_OK;
 }
 
+int dg_merkle_diff_take(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
+                        const dg_store* sb, int side, uint64_t* out_keys, uint64_t cap, uint64_t* offs,
+                        dg_store* rows, uint64_t* n_out, uint64_t* n_total) {
+  if (!e) return fail(DG_E_INVAL, "null engine");
+  TRY(check_merkle(a, "dg_merkle_diff_take a"));
+  TRY(check_merkle(b, "dg_merkle_diff_take b"));
+  TRY(same_tree_shape(a, b, "dg_merkle_diff_take"));
+  TRY(check_store(sa, "dg_merkle_diff_take sa"));
+  TRY(check_store(sb, "dg_merkle_diff_take sb"));
+  if (side != 0 && side != 1) return fail(DG_E_INVAL, "dg_merkle_diff_take: side %d (0: sa, 1: sb)", side);
+  if (!n_out) return fail(DG_E_INVAL, "dg_merkle_diff_take: null n_out");
+  if (cap && !out_keys) return fail(DG_E_INVAL, "dg_merkle_diff_take: null out_keys");
+  if (cap && !offs) return fail(DG_E_INVAL, "dg_merkle_diff_take: null offs");
+  if (!rows) return fail(DG_E_INVAL, "dg_merkle_diff_take: null rows");
+  if (rows->cap && (!rows->key || !rows->val || !rows->ts || !rows->node || !rows->cnt))
+    return fail(DG_E_INVAL, "dg_merkle_diff_take: null column with cap=%llu", (unsigned long long)rows->cap);
+  TRY(set_device(e));
+  TRY(settle(e));
+  rows->n = 0;
+  TRY(ensure_tmp(e, diff_take_scratch_words(a->depth, sa->n, sb->n) * sizeof(u64)));
+  TRY(ensure_diff_bsum(e, diff_groups(a->depth)));
+  TRY(ensure_diff_rsum(e, diff_groups(a->depth)));
+  {
+    const u64 g = e->diff_bsum.cap, rg = e->diff_rsum.cap;
+    u64* use = e->diff_bsum.as<u64>() + (e->diff_parity ? g : 0);
+    u64* zero = e->diff_bsum.as<u64>() + (e->diff_parity ? 0 : g);
+    u64* ruse = e->diff_rsum.as<u64>() + (e->diff_rparity ? rg : 0);
+    u64* rzero = e->diff_rsum.as<u64>() + (e->diff_rparity ? 0 : rg);
+    e->diff_parity ^= 1;
+    e->diff_rparity ^= 1;
+    HIP_TRY(launch_merkle_diff_take(merkle_of(a), rows_of(sa), merkle_of(b), rows_of(sb), (u32)side, out_keys, cap,
+                                    offs, rows_out_of(rows), rows->cap, e->tmp.as<u64>(), use, zero, ruse, rzero, g,
+                                    rg, e->d_counts, e->stream));
+  }
+  TRY(read_counts(e));  // the key total and the kept keys' rows, one wait
+  const u64 total = e->h_counts[JC_ROWS];
+  if (total >= DIFF_MISMATCH) {
+    *n_out = 0;
+    if (n_total) *n_total = 0;
+    return fail(DG_E_INVAL, "dg_merkle_diff_take: a tree counts more rows than its store holds "
+                            "(the store is not the one the tree was built / updated against)");
+  }
+  *n_out = std::min<u64>(total, cap);
+  if (n_total) *n_total = total;
+  rows->n = e->h_counts[DT_ROWS];
+  if (rows->n > rows->cap)
+    return fail(DG_E_CAPACITY, "dg_merkle_diff_take: %llu rows needed, room for %llu", (unsigned long long)rows->n,
+                (unsigned long long)rows->cap);
+  return DG_OK;
+}
+
 int dg_merkle_diff_async(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
                          const dg_store* sb, uint64_t* out_keys, uint64_t cap, uint64_t* d_total) {
   if (!e) return fail(DG_E_INVAL, "null engine");

@@ -54,6 +54,10 @@ struct dg_engine {
   // previous call used (no memset launch per diff)
   Buf diff_bsum;
   int diff_parity = 0;
+  // dg_merkle_diff_take's per-group row sums, kept the same way with a parity of their own:
+  // only a take adds into them, and only a take's write kernel zeroes the previous take's
+  Buf diff_rsum;
+  int diff_rparity = 0;
   u32 epoch = 0;
   // small device counters + pinned host mirror.  d_counts[0..8) and ticket[0..16) are one
   // device allocation (ticket == (u32*)(d_counts + 8)), so a synchronous call brings its
@@ -154,6 +158,9 @@ enum MutateCount {  // mutate_count_kernel's last tile
 enum MarkCount {    // mark.hip
   MK_USED = 0,      // ids used
   MK_UNKNOWN = 1,   // rows whose id is not in the table
+};
+enum DiffTakeCount {  // merkle_diff_take_write_kernel (the key total is JC_ROWS, as the diff's)
+  DT_ROWS = 1,         // the kept keys' rows in the chosen store
 };
 // (the streaming store diff: enum SdCount, dg_launch.h -- its kernels use the names too)
 constexpr int HC_KFOLD_FLAG = 10;  // h_counts only: kfold_pass copies its flag word here
@@ -278,6 +285,9 @@ inline int ensure_kdz(dg_engine* e, size_t bytes) {
 // the full diff's two group-sum buffers (see dg_engine::diff_bsum)
 inline int ensure_diff_bsum(dg_engine* e, u64 groups) {
   return grow(e, &e->diff_bsum, groups, 2 * sizeof(u64), 0, GROW_ZERO, "hipMalloc of %llu diff group sums failed");
+}
+inline int ensure_diff_rsum(dg_engine* e, u64 groups) {
+  return grow(e, &e->diff_rsum, groups, 2 * sizeof(u64), 0, GROW_ZERO, "hipMalloc of %llu diff group sums failed");
 }
 // pinned host staging (kernel descriptors, digit histograms)
 inline int ensure_stage(dg_engine* e, size_t bytes) {

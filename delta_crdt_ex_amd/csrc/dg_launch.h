@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dg_device.h"
+#include "dg_diff_scratch.h"
 
 namespace dg {
 
@@ -601,19 +602,7 @@ struct SmallTailArgs {
 };
 constexpr u64 SMALL_TILE = 2048;  // rows per splice tile of the tail kernel
 hipError_t launch_small_tail(const SmallTailArgs& p, hipStream_t st);
-constexpr int DIFF_BLOCK = 256;
-#ifndef DG_DIFF_SUB
-#define DG_DIFF_SUB 12
-#endif
-constexpr u32 DIFF_SUB = DG_DIFF_SUB;  // levels a diff workgroup descends: subtrees of 2^DIFF_SUB buckets
-inline u32 diff_sub(u32 depth) { return depth < DIFF_SUB ? depth : DIFF_SUB; }
-inline u64 diff_tiles(u32 depth) { return 1ull << (depth - diff_sub(depth)); }
-// subtree boundaries in both stores, per-subtree counts, then the differing keys staged
-// per subtree (at most one per row of either store), then the group sums
-inline u64 diff_groups(u32 depth) { return (diff_tiles(depth) + DIFF_BLOCK - 1) / DIFF_BLOCK; }  // of DIFF_BLOCK subtrees
-inline u64 diff_scratch_words(u32 depth, u64 na, u64 nb) {
-  return 2 * (diff_tiles(depth) + 1) + diff_tiles(depth) + na + nb + 1;
-}
+// (the full diff's tiling and scratch sizes: dg_diff_scratch.h)
 // a subtree whose tree row counts overrun a store adds this to the total (no keys): at most
 // 2^18 subtrees (depth 30) keep the sum of markers below 2^63, and no total of real keys
 // reaches it (deltagpu.h DG_DIFF_MISMATCH)
@@ -622,6 +611,19 @@ constexpr u64 DIFF_MISMATCH = 1ull << 44;
 hipError_t launch_merkle_diff(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb,
                               u64* out_keys, u64 cap, u64* scratch, u64* bsum, u64* bsum_zero, u64 nzero,
                               u64* d_count, hipStream_t st);
+// The take form (dg_merkle_diff_take): the same diff, and the rows of the kept keys in one of
+// the two stores.  Beside each differing key in scratch sits its located run in that store, one
+// word: the run's first row in the low DIFF_LOC_LEN bits (a store holds fewer than 2^44 rows),
+// its length above them (a bucket holds at most 65535 rows; 0: the store lacks the key).
+constexpr u32 DIFF_LOC_LEN = 44;
+// (its scratch: diff_take_scratch, dg_diff_scratch.h)
+// side: 0 the rows of sa, 1 of sb.  offs[0 .. kept] = the kept keys' row offsets (kept =
+// min(total, cap)); rows written below rcap only; d_count[0] = the key total, d_count[1] =
+// the kept keys' rows.  rsum / rsum_zero (nrzero words): the per-group row sums, as bsum / bsum_zero.
+hipError_t launch_merkle_diff_take(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb, u32 side,
+                                   u64* out_keys, u64 cap, u64* offs, const RowsOut& rows, u64 rcap, u64* scratch,
+                                   u64* bsum, u64* bsum_zero, u64* rsum, u64* rsum_zero, u64 nzero, u64 nrzero,
+                                   u64* d_count, hipStream_t st);
 // dg_merkle_continue_home's one-workgroup hop (merkle_cont.hip cont_hop_kernel<false>): limits,
 // result kinds (home[0]) and arguments
 constexpr u32 CS_IN = 4096, CS_B = 512;  // entries / pairs in, buckets in (leaf form)

@@ -85,12 +85,18 @@ __device__ __forceinline__ u64 wave_bucket_start(const MerkleT& t, const u64* ke
 // Merge keys[ia, ie) of store A (rows) with B, where B is either a store (rows) or a
 // list of (key, leaf) pairs; emit the keys present on one side only or with different
 // leaves.  WRITE: store them at out[o..) (only below cap); returns the count.
-template <bool B_LEAVES, bool WRITE>
-__device__ u32 merge_bucket(const Rows& A, const TermH& tha, u64 ia, u64 ie, const Rows& B,
-                            const TermH& thb, const u64* bk, const u64* bh, u64 jb, u64 je,
-                            u64* out, u64 o, u64 cap) {
+// LOC (the full diff's take form): each emitted key's run in the chosen store (side 0: A,
+// 1: B) is known here as the walk's start and end, so it goes to loc[o..) beside the key
+// as row | length << DIFF_LOC_LEN (length 0: the store lacks the key) and its length is added to
+// *nrows -- the key is never searched for again.
+template <bool B_LEAVES, bool WRITE, bool LOC>
+__device__ __forceinline__ u32 merge_bucket_impl(const Rows& A, const TermH& tha, u64 ia, u64 ie, const Rows& B,
+                                                 const TermH& thb, const u64* bk, const u64* bh, u64 jb,
+                                                 u64 je, u64* out, u64 o, u64 cap, u64* loc, u32 side,
+                                                 u32* nrows) {
   u32 c = 0;
   while (ia < ie || jb < je) {
+    [[maybe_unused]] const u64 ia0 = ia, jb0 = jb;
     const u64 ka = ia < ie ? A.key[ia] : ~0ull;
     const u64 kb = jb < je ? (B_LEAVES ? bk[jb] : B.key[jb]) : ~0ull;
     const bool has_a = ia < ie && (jb >= je || ka <= kb);
@@ -108,10 +114,32 @@ __device__ u32 merge_bucket(const Rows& A, const TermH& tha, u64 ia, u64 ie, con
     }
     if (!(has_a && has_b) || ha != hb) {
       if (WRITE && o + c < cap) out[o + c] = k;
+      if constexpr (LOC) {
+        const u64 len = side ? jb - jb0 : ia - ia0;
+        if (WRITE && o + c < cap) loc[o + c] = (side ? jb0 : ia0) | (len << DIFF_LOC_LEN);
+        if (nrows) *nrows += (u32)len;
+      }
       c++;
     }
   }
   return c;
+}
+
+template <bool B_LEAVES, bool WRITE>
+__device__ u32 merge_bucket(const Rows& A, const TermH& tha, u64 ia, u64 ie, const Rows& B,
+                            const TermH& thb, const u64* bk, const u64* bh, u64 jb, u64 je,
+                            u64* out, u64 o, u64 cap) {
+  return merge_bucket_impl<B_LEAVES, WRITE, false>(A, tha, ia, ie, B, thb, bk, bh, jb, je, out, o, cap, nullptr, 0,
+                                                   nullptr);
+}
+
+// two stores, every key written (the full diff's global path)
+template <bool WRITE>
+__device__ u32 merge_bucket_loc(const Rows& A, const TermH& tha, u64 ia, u64 ie, const Rows& B,
+                                const TermH& thb, u64 jb, u64 je, u64* out, u64 o, u64* loc, u32 side,
+                                u32* nrows) {
+  return merge_bucket_impl<false, WRITE, true>(A, tha, ia, ie, B, thb, nullptr, nullptr, jb, je, out, o, ~0ull, loc,
+                                               side, nrows);
 }
 
 // ---------------------------------------------------------------- hand-offs

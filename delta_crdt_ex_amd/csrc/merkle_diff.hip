@@ -77,6 +77,25 @@ struct DiffArgs {
   u64* d_count;
 };
 
+// The take form (dg_merkle_diff_take): beside each differing key the count kernel stores
+// where the key's run lies in the chosen store -- its first row in the low DIFF_LOC_LEN bits (a
+// store holds fewer than 2^44 rows), its length above them (a bucket holds at most 65535;
+// 0: the store lacks the key) -- and the subtree's sum of those lengths, kept as cnt / bsum
+// are; the write kernel scans the lengths into offs and copies the rows.
+struct DiffTakeArgs : DiffArgs {
+  u64* loc;    // scratch: keys[x]'s run in the chosen store
+  u64* rcnt;   // per subtree: the rows of its differing keys in the chosen store
+  u64* rsum;   // per DB subtrees: the sum of their row counts (zero when the count kernel starts)
+  u64* rzero;  // the previous take's sums, zeroed by the write kernel
+  u64 nrzero;  // ... all of its words
+  u32 side;    // 0: the rows of sa, 1: of sb
+  u64* offs;   // cap + 1 row offsets
+  RowsOut rows;
+  u64 rcap;
+};
+template <bool TAKE>
+using DiffP = std::conditional_t<TAKE, DiffTakeArgs, DiffArgs>;
+
 // the counts of a thread's 16 buckets (u16) as 8 words of two halves: 32 bytes at
 // c + first, one path for every subtree size (the counts array holds at least 16 entries,
 // deltagpu.h); mask_counts16 zeroes what the thread does not own, AFTER the round trip's
@@ -132,7 +151,8 @@ __device__ u64 g_df_stamps[4096 * 8];
   } while (0)
 #endif
 
-__global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_kernel(DiffArgs p) {
+template <bool TAKE>
+__global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_kernel(DiffP<TAKE> p) {
   __shared__ u32 s_wave[DB / WAVE + 1];
   __shared__ u32 s_da[DCAP], s_db[DCAP];  // a differing bucket's first row in A / B (from the subtree's)
   __shared__ u32 s_dp[DCAP + 1];          // its first staged row
@@ -199,7 +219,10 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
   if ((u32)tid < nna) s_nha[tid] = hna;
   if ((u32)tid < nnb) s_nhb[tid] = hnb;
   if (ra == rb) {  // uniform: the whole subtree matches (the bounds are written anyway)
-    if (tid == 0) p.cnt[tile] = 0;
+    if (tid == 0) {
+      p.cnt[tile] = 0;
+      if constexpr (TAKE) p.rcnt[tile] = 0;
+    }
     return;
   }
   DSTAMP(1);
@@ -306,6 +329,7 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
     // the marker reaches the total, which the host reports as an input error.
     if (tid == 0) {
       p.cnt[tile] = DIFF_MISMATCH;
+      if constexpr (TAKE) p.rcnt[tile] = 0;
       atomicAdd((unsigned long long*)&p.bsum[tile / DB], (unsigned long long)DIFF_MISMATCH);
     }
     return;
@@ -422,6 +446,9 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
     // (the merge used to run twice for every lane: count, then write)
     constexpr u32 KR = 4;
     u64 kr0 = 0, kr1 = 0, kr2 = 0, kr3 = 0;
+    // (take form) the kept keys' located runs, and the lane's rows of its differing keys
+    [[maybe_unused]] u64 lr0 = 0, lr1 = 0, lr2 = 0, lr3 = 0;
+    [[maybe_unused]] u32 nrows = 0;
     auto merge = [&](bool write, u32 o) {
       u32 k2 = 0;
       // (a lane's buckets are contiguous, so the lanes' outputs in lane order are in
@@ -430,7 +457,12 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
       for (u32 d = tid * per; d < d1; d++) {
         const u32 na = s_dn[d] >> 16;
         u32 ia = s_dp[d], ie = ia + na, jb = ie, je = s_dp[d + 1];
+        // (take form) a staged index of the chosen store's rows of this bucket + lbase = the
+        // row's index in the store: from the bucket's list entry, once per bucket
+        [[maybe_unused]] u64 lbase = 0;
+        if constexpr (TAKE) lbase = p.side ? s_bnd[1] + s_db[d] - ie : s_bnd[0] + s_da[d] - ia;
         while (ia < ie || jb < je) {
+          [[maybe_unused]] const u32 ia0 = ia, jb0 = jb;
           // (ia, jb sit on run heads; every read of the step at clamped indices, together)
           const u32 xa = min(ia, R - 1), xb = min(jb, R - 1);
           const u64 ka0 = s_k[xa], kb0 = s_k[xb], ha0 = s_h[xa], hb0 = s_h[xb];
@@ -448,13 +480,26 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
             else for (; jb < je && s_k[jb] == k; jb++) {}
           }
           if (!(pa && pb) || ha != hb) {
+            [[maybe_unused]] u64 lw = 0;
+            if constexpr (TAKE) {  // (a run the store lacks: length 0 at the row it would sit at)
+              const u32 len = p.side ? jb - jb0 : ia - ia0;
+              lw = (lbase + (p.side ? jb0 : ia0)) | ((u64)len << DIFF_LOC_LEN);
+              if (!write) nrows += len;
+            }
             if (write) {
               p.keys[s_bnd[0] + s_bnd[1] + o + k2] = k;
+              if constexpr (TAKE) p.loc[s_bnd[0] + s_bnd[1] + o + k2] = lw;
             } else {
               kr0 = k2 == 0 ? k : kr0;
               kr1 = k2 == 1 ? k : kr1;
               kr2 = k2 == 2 ? k : kr2;
               kr3 = k2 == 3 ? k : kr3;
+              if constexpr (TAKE) {
+                lr0 = k2 == 0 ? lw : lr0;
+                lr1 = k2 == 1 ? lw : lr1;
+                lr2 = k2 == 2 ? lw : lr2;
+                lr3 = k2 == 3 ? lw : lr3;
+              }
             }
             k2++;
           }
@@ -465,7 +510,20 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
     const u32 c = merge(false, 0);
     DSTAMP(5);
     u32 t2;
-    const u32 o = block_excl_scan<DB>(c, s_wave, &t2);
+    u32 o;
+    if constexpr (TAKE) {
+      // keys and rows in one scan: neither exceeds the staged rows (R <= RCAP < 2^16)
+      static_assert(RCAP < (1u << 16), "a subtree's staged keys and rows fit 16 bits each");
+      u32 t;
+      o = block_excl_scan<DB>(c | (nrows << 16), s_wave, &t) & 0xFFFFu;
+      t2 = t & 0xFFFFu;
+      if (tid == 0) {
+        p.rcnt[tile] = t >> 16;
+        if (t >> 16) atomicAdd((unsigned long long*)&p.rsum[tile / DB], (unsigned long long)(t >> 16));
+      }
+    } else {
+      o = block_excl_scan<DB>(c, s_wave, &t2);
+    }
     if (tid == 0) {
       p.cnt[tile] = t2;
       if (t2) atomicAdd((unsigned long long*)&p.bsum[tile / DB], (unsigned long long)t2);
@@ -480,6 +538,13 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
       if (c > 1) dst[1] = kr1;
       if (c > 2) dst[2] = kr2;
       if (c > 3) dst[3] = kr3;
+      if constexpr (TAKE) {
+        u64* ldst = p.loc + (s_bnd[0] + s_bnd[1]) + o;
+        if (c > 0) ldst[0] = lr0;
+        if (c > 1) ldst[1] = lr1;
+        if (c > 2) ldst[2] = lr2;
+        if (c > 3) ldst[3] = lr3;
+      }
     }
     DSTAMP(6);
     return;
@@ -487,6 +552,7 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
   // more differing rows or buckets than the LDS lists hold: each thread merges its owned
   // differing buckets over global memory
   u32 c = 0;
+  [[maybe_unused]] u32 nrows = 0;  // (take form) the thread's rows of its differing keys
   for (int pass = 0; pass < 2; pass++) {
     u32 o = 0;
     if (pass == 1) {
@@ -496,6 +562,15 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
         p.cnt[tile] = t2;
         if (t2) atomicAdd((unsigned long long*)&p.bsum[tile / DB], (unsigned long long)t2);
       }
+      if constexpr (TAKE) {  // (a thread's 16 buckets hold < 2^20 rows, the subtree < 2^28)
+        u32 rt;
+        __syncthreads();  // s_wave is read until here
+        block_excl_scan<DB>(nrows, s_wave, &rt);
+        if (tid == 0) {
+          p.rcnt[tile] = rt;
+          if (rt) atomicAdd((unsigned long long*)&p.rsum[tile / DB], (unsigned long long)rt);
+        }
+      }
     }
     u32 k2 = 0, ra = offa, rb = offb;
     for (u32 i = 0; i < OWN; i++) {
@@ -504,7 +579,14 @@ __global__ __launch_bounds__(DB, DIFF_OCC * DB / 256) void merkle_diff_count_ker
       const u64 bi = bucket0 + (u64)tid * OWN + i;
       const u32 x = bi - bucket0 < nb ? p.ta.counts[bi] : 0u, y = bi - bucket0 < nb ? p.tb.counts[bi] : 0u;
       if (mine >> i & 1u) {
-        if (pass == 0)
+        if constexpr (TAKE) {
+          if (pass == 0)
+            k2 += merge_bucket_loc<false>(p.sa, p.ta.th, a0 + ra, a0 + ra + x, p.sb, p.tb.th, c0 + rb,
+                                          c0 + rb + y, nullptr, 0, nullptr, p.side, &nrows);
+          else
+            k2 += merge_bucket_loc<true>(p.sa, p.ta.th, a0 + ra, a0 + ra + x, p.sb, p.tb.th, c0 + rb,
+                                         c0 + rb + y, p.keys + a0 + c0, o + k2, p.loc + a0 + c0, p.side, nullptr);
+        } else if (pass == 0)
           k2 += merge_bucket<false, false>(p.sa, p.ta.th, a0 + ra, a0 + ra + x, p.sb, p.tb.th,
                                            nullptr, nullptr, c0 + rb, c0 + rb + y, nullptr, 0, 0);
         else
@@ -581,7 +663,146 @@ __global__ __launch_bounds__(WAVE) void merkle_diff_write_kernel(DiffArgs p) {
   }
 }
 
+// The take form's write kernel: the same offsets, and beside the key offset a row offset out
+// of rcnt / rsum by the same sums (every subtree before the one `cap` cuts is kept whole, so
+// its row count is exact).  The wave then goes through the subtree's kept keys 64 at a time:
+// a wave scan of the run lengths on top of the row offset gives offs, and the lanes copy the
+// chunk's rows, four rows per lane in flight, each finding its key in the chunk's 64 offsets
+// in LDS.  The subtree `cap` cuts -- or the last one when none is cut -- writes offs[kept] and
+// the row total.  No key at or past cap and no row at or past rcap is written, and nothing
+// where any subtree met a store its tree does not describe.
+__global__ __launch_bounds__(WAVE) void merkle_diff_take_write_kernel(DiffTakeArgs p) {
+  __shared__ u32 s_off[WAVE];
+  __shared__ u64 s_row[WAVE];
+  const int lane = threadIdx.x;
+  const u64 tile = blockIdx.x, grp = tile / DB, g0 = grp * DB;
+  if (tile == 0) {  // the previous calls' group sums: zero for the next ones
+    for (u64 x = lane; x < p.nzero; x += WAVE) p.bzero[x] = 0;
+    for (u64 x = lane; x < p.nrzero; x += WAVE) p.rzero[x] = 0;
+  }
+  const bool last = tile + 1 == p.ntiles;
+  constexpr int CQ = DB / WAVE;
+  const u64 n = p.cnt[tile];
+  const u64 sa = p.bnd[tile], sb = p.bnd[p.ntiles + 1 + tile];
+  u64 c[CQ], r[CQ];
+#pragma unroll
+  for (int q = 0; q < CQ; q++) {
+    const u64 x = g0 + (u64)lane + (u64)q * WAVE;
+    c[q] = p.cnt[x < tile ? x : tile];
+    r[q] = p.rcnt[x < tile ? x : tile];
+  }
+  const u64 b0 = p.bsum[(u64)lane < grp ? (u64)lane : 0ull], r0 = p.rsum[(u64)lane < grp ? (u64)lane : 0ull];
+  u64 before = (u64)lane < grp ? b0 : 0ull, rbefore = (u64)lane < grp ? r0 : 0ull;
+#pragma unroll
+  for (int q = 0; q < CQ; q++) {
+    const bool in = g0 + (u64)lane + (u64)q * WAVE < tile;
+    before += in ? c[q] : 0ull;
+    rbefore += in ? r[q] : 0ull;
+  }
+  for (u64 x = lane + WAVE; x < grp; x += WAVE) before += p.bsum[x], rbefore += p.rsum[x];
+  // every group's sum as well (the same words for up to 64 groups): a marker anywhere in the
+  // tree, not only upstream, and this call writes nothing at all
+  const u64 ng = (p.ntiles + DB - 1) / DB;
+  const u64 a0 = p.bsum[(u64)lane < ng ? (u64)lane : 0ull];
+  u64 all = (u64)lane < ng ? a0 : 0ull;
+  for (u64 x = lane + WAVE; x < ng; x += WAVE) all += p.bsum[x];
+#pragma unroll
+  for (int d = WAVE / 2; d >= 1; d >>= 1) {
+    before += __shfl_xor(before, d, WAVE);
+    rbefore += __shfl_xor(rbefore, d, WAVE);
+    all += __shfl_xor(all, d, WAVE);
+  }
+  if (last && lane == 0) p.d_count[0] = before + n;
+  if (all >= DIFF_MISMATCH) return;  // (the host reports the input error)
+  // the subtree that writes offs[kept] and the row total: the one cap cuts, else the last
+  const bool fin = (before <= p.cap && p.cap < before + n) || (last && before + n <= p.cap);
+  const u64 m = before < p.cap ? (n < p.cap - before ? n : p.cap - before) : 0ull;  // keys kept here
+  if (m == 0 && !fin) return;
+  const Rows& S = p.side ? p.sb : p.sa;
+  const u64 src = sa + sb;
+  u64 rbase = rbefore;  // the row offset of the chunk's first key
+  for (u64 x0 = 0; x0 < m; x0 += WAVE) {
+    const u64 x = x0 + lane;
+    const bool in = x < m;
+    const u64 k = p.keys[src + (in ? x : m - 1)], w = p.loc[src + (in ? x : m - 1)];
+    const u32 len = in ? (u32)(w >> DIFF_LOC_LEN) : 0u;
+    const u32 inc = wave_incl_scan(len), T = (u32)__builtin_amdgcn_readlane((int)inc, WAVE - 1);
+    s_off[lane] = inc - len;
+    s_row[lane] = w & ((1ull << DIFF_LOC_LEN) - 1);
+    if (in) {
+      p.out[before + x] = k;
+      p.offs[before + x] = rbase + (inc - len);
+    }
+    __syncthreads();
+    constexpr int RQ = 4;  // rows per lane in flight
+    for (u32 q0 = 0; q0 < T; q0 += RQ * WAVE) {
+      Row v[RQ];
+#pragma unroll
+      for (int q = 0; q < RQ; q++) {
+        const u32 i = q0 + (u32)q * WAVE + lane, ic = i < T ? i : T - 1;
+        u32 lo = 0;  // the last key of the chunk whose first row is at or before row ic
+#pragma unroll
+        for (u32 step = WAVE / 2; step >= 1; step >>= 1) lo += s_off[lo + step] <= ic ? step : 0u;
+        v[q] = load_row(S, s_row[lo] + (ic - s_off[lo]));
+      }
+#pragma unroll
+      for (int q = 0; q < RQ; q++) {
+        const u32 i = q0 + (u32)q * WAVE + lane;
+        const u64 dst = rbase + i;
+        if (i < T && dst < p.rcap) {
+          p.rows.key[dst] = v[q].key;
+          p.rows.val[dst] = v[q].val;
+          p.rows.ts[dst] = v[q].ts;
+          p.rows.node[dst] = v[q].node;
+          p.rows.cnt[dst] = v[q].cnt;
+        }
+      }
+    }
+    rbase += T;
+    __syncthreads();  // (the next chunk overwrites the offsets)
+  }
+  if (fin && lane == 0) {
+    if (p.offs) p.offs[before + m] = rbase;
+    p.d_count[1] = rbase;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_merkle_diff_take(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb, u32 side,
+                                   u64* out_keys, u64 cap, u64* offs, const RowsOut& rows, u64 rcap, u64* scratch,
+                                   u64* bsum, u64* bsum_zero, u64* rsum, u64* rsum_zero, u64 nzero, u64 nrzero,
+                                   u64* d_count, hipStream_t st) {
+  DiffTakeArgs p;
+  p.ta = a;
+  p.tb = b;
+  p.sa = sa;
+  p.sb = sb;
+  p.out = out_keys;
+  p.cap = cap;
+  p.ntiles = diff_tiles(a.depth);
+  p.sub = diff_sub(a.depth);
+  const DiffTakeScratch ts = diff_take_scratch(a.depth, sa.n, sb.n);
+  p.bnd = scratch + ts.bnd;
+  p.cnt = scratch + ts.cnt;
+  p.keys = scratch + ts.keys;
+  p.loc = scratch + ts.loc;
+  p.rcnt = scratch + ts.rcnt;
+  p.bsum = bsum;
+  p.bzero = bsum_zero;
+  p.rsum = rsum;
+  p.rzero = rsum_zero;
+  p.nzero = nzero;
+  p.nrzero = nrzero;
+  p.d_count = d_count;
+  p.side = side;
+  p.offs = offs;
+  p.rows = rows;
+  p.rcap = rcap;
+  hipLaunchKernelGGL(merkle_diff_count_kernel<true>, dim3((unsigned)p.ntiles), dim3(DB), 0, st, p);
+  hipLaunchKernelGGL(merkle_diff_take_write_kernel, dim3((unsigned)p.ntiles), dim3(WAVE), 0, st, p);
+  return hipGetLastError();
+}
 
 hipError_t launch_merkle_diff(const MerkleT& a, const Rows& sa, const MerkleT& b, const Rows& sb,
                               u64* out_keys, u64 cap, u64* scratch, u64* bsum, u64* bsum_zero, u64 nzero,
@@ -603,7 +824,7 @@ hipError_t launch_merkle_diff(const MerkleT& a, const Rows& sa, const MerkleT& b
   p.nzero = nzero;
   p.d_count = d_count;
   // (the subtree bounds are searched inside the count kernel)
-  hipLaunchKernelGGL(merkle_diff_count_kernel, dim3((unsigned)p.ntiles), dim3(DB), 0, st, p);
+  hipLaunchKernelGGL(merkle_diff_count_kernel<false>, dim3((unsigned)p.ntiles), dim3(DB), 0, st, p);
   hipLaunchKernelGGL(merkle_diff_write_kernel, dim3((unsigned)p.ntiles), dim3(WAVE), 0, st, p);
   return hipGetLastError();
 }

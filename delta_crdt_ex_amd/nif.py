@@ -116,6 +116,8 @@ _SIGS = {
                                    C.POINTER(dgr_changed), C.POINTER(dgr_diffs)]),
     "dgr_mutate_batch_diffs": (I32, [VP, U64, C.c_uint32, U64, VP, VP, VP, VP, C.POINTER(dgr_changed),
                                      C.POINTER(dgr_diffs)]),
+    "dgr_sync_from": (I32, [VP, U64, VP, U64, U64, C.POINTER(dgr_changed), PU64]),
+    "dgr_sync_from_diffs": (I32, [VP, U64, VP, U64, U64, C.POINTER(dgr_changed), C.POINTER(dgr_diffs), PU64]),
     "dgr_join_deltas": (I32, [VP, U64, I32, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP), PU64,
                               C.POINTER(dgr_changed)]),
     "dgr_join_deltas_diffs": (I32, [VP, U64, I32, C.POINTER(dg_store), C.POINTER(dg_context), C.POINTER(VP),
@@ -488,6 +490,47 @@ def join_delta_diffs(state: State, version: int, dots, value, keys):
     """join_delta that also returns on_diffs' list, from the device's reads of the changed
     keys before and after the join (dgr_join_delta_diffs): no old struct is read."""
     return join_delta(state, version, dots, value, keys, _diffs=True)
+
+
+def sync_from(dst: State, dst_version: int, src: State, src_version: int, max_sync_size="infinite",
+              _diffs: bool = False):
+    """sync_from(dst, dst_version, src, src_version, max_sync_size | :infinite) -> {:ok, version',
+    new_dots, changed, n_total}: one anti-entropy exchange from `src` toward `dst`, two replicas
+    attached to one engine, device to device (dgr_sync_from): the trees' diff, src's rows of the
+    first max_sync_size differing keys and their join into dst, with no row turned into a term.
+    n_total is the untruncated number of differing keys; run another round while it exceeds
+    max_sync_size.  Marshals exactly as join_delta does."""
+    if not isinstance(dst, State) or not isinstance(src, State):
+        return _err(_abi.DG_E_INVAL)
+    eng = dst.engine
+    if max_sync_size in ("infinite", None):
+        ms = 0
+    elif isinstance(max_sync_size, int) and max_sync_size > 0:
+        ms = max_sync_size
+    else:
+        return _err(_abi.DG_E_INVAL)
+    if eng.lib.dgr_state_has_tree(dst.ptr) and eng.lib.dgr_state_has_tree(src.ptr) and src.engine is eng:
+        rc = eng.refresh_terms()
+        if rc:
+            return _err(rc)
+    ch, tot = dgr_changed(), C.c_uint64()
+    if _diffs:
+        df = dgr_diffs()
+        rc = eng.lib.dgr_sync_from_diffs(dst.ptr, dst_version, src.ptr, src_version, ms, C.byref(ch), C.byref(df),
+                                         C.byref(tot))
+        if rc:
+            return _err(rc)
+        res = _diffs_result(eng, ch, df)
+        return res[:4] + (int(tot.value),) + res[4:]
+    rc = eng.lib.dgr_sync_from(dst.ptr, dst_version, src.ptr, src_version, ms, C.byref(ch), C.byref(tot))
+    if rc:
+        return _err(rc)
+    return _changed_result(eng, ch) + (int(tot.value),)
+
+
+def sync_from_diffs(dst: State, dst_version: int, src: State, src_version: int, max_sync_size="infinite"):
+    """sync_from that also returns on_diffs' list: {:ok, version', new_dots, changed, n_total, diffs}."""
+    return sync_from(dst, dst_version, src, src_version, max_sync_size, _diffs=True)
 
 
 def join_deltas(state: State, version: int, deltas, _diffs: bool = False):

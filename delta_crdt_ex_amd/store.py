@@ -1043,6 +1043,44 @@ class Engine:
         keys = out[: n.value].clone()
         return (keys, int(tot.value)) if with_total else keys
 
+    def merkle_diff_take(self, a: MerkleTree, b: MerkleTree, side: int = 1, cap: int | None = None,
+                         rows: Store | None = None):
+        """dg_merkle_diff_take: merkle_diff(a, b, cap) answered with the kept keys' rows in
+        a's store (side 0) or b's (side 1), in one call.  Returns (keys, rows, offs, total):
+        rows offs[i]..offs[i + 1] of `rows` are keys[i]'s (offs has len(keys) + 1 entries),
+        bit-identical to take_keys(store, keys); total is the untruncated key count.  `rows`
+        is sized here when not given, and a DG_E_CAPACITY is retried once with the size the
+        call asked for."""
+        self._order()
+        if cap is None:
+            cap = a.n_keys + b.n_keys
+        cap = int(cap)
+        out = getattr(self, "_diff_out", None)
+        if out is None or out.numel() < max(cap, 1):
+            out = self._diff_out = torch.empty(max(cap, 1), dtype=_I64, device=self.device)
+        offs = torch.empty(cap + 1, dtype=_I64, device=self.device)
+        store = b.store if side else a.store
+        if rows is None:
+            # a sync delta holds a few rows per key (take_keys sizes its output the same way)
+            rows = Store.empty(min(max(store.n, 1), max(4 * cap, 256)), self.device)
+        n, tot = C.c_uint64(), C.c_uint64()
+        ta, tb, sa, sb = a.abi(), b.abi(), a.store.abi(), b.store.abi()
+
+        def call(r):
+            so = r.abi()
+            rc = self.lib.dg_merkle_diff_take(self.h, C.byref(ta), C.byref(sa), C.byref(tb), C.byref(sb),
+                                              int(side), _ptr(out, _abi.P64), cap, _ptr(offs, _abi.P64),
+                                              C.byref(so), C.byref(n), C.byref(tot))
+            return rc, so
+
+        rc, so = call(rows)
+        if rc == _abi.DG_E_CAPACITY and int(so.n) > rows.cap:
+            rows = Store.empty(int(so.n), self.device)
+            rc, so = call(rows)
+        check(rc)
+        rows._set(so)
+        return out[: n.value].clone(), rows, offs[: n.value + 1], int(tot.value)
+
     def prepare_merkle_diff(self, a: MerkleTree, b: MerkleTree, out: torch.Tensor, cap: int,
                             d_total: torch.Tensor):
         """Pre-marshal dg_merkle_diff_async for repeated launches (benchmark loops, a

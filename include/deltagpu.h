@@ -707,6 +707,28 @@ int dg_merkle_diff(dg_engine* e, const dg_merkle* a, const dg_store* sa, const d
                    const dg_store* sb, uint64_t* out_keys, uint64_t cap, uint64_t* n_out,
                    uint64_t* n_total);
 
+/* dg_merkle_diff answered with its rows: out_keys, *n_out and *n_total are exactly
+ * dg_merkle_diff's for the same arguments, and `rows` receives the rows of one of the two
+ * stores (side 0: sa, 1: sb; anything else DG_E_INVAL) whose key is among
+ * out_keys[0, *n_out), in store order, bit-identical to dg_take_keys(store, out_keys,
+ * *n_out); rows->n = their number.  The workgroup that finds a key differing has the
+ * key's rows in hand and hands their place over, so no key is searched for again: one
+ * launch chain, one host wait (the sender's `Map.take(state, keys)` of
+ * causal_crdt.ex:109-118 in the call that found the keys).
+ *   offs : cap + 1 entries; rows [offs[i], offs[i+1]) are out_keys[i]'s (a key the store
+ *          lacks: an empty range); offs[*n_out] == rows->n.
+ * More rows than rows->cap: DG_E_CAPACITY; *n_out, *n_total and out_keys are valid,
+ * rows->n is the number needed, `rows` and offs hold nothing.  cap == 0 is allowed
+ * (*n_out = 0, rows->n = 0).  out_keys, offs and the row columns may be device memory or
+ * host memory from dg_host_alloc.  A tree that counts more rows than its store holds is
+ * handled as by dg_merkle_diff: DG_E_INVAL, no row read past a store.  DG_E_INVAL before
+ * any launch: a null engine, null n_out, cap with null out_keys or null offs, null rows, a
+ * null column with rows->cap > 0, trees of different shape.  Only reads the stores and
+ * trees.  Synchronous. */
+int dg_merkle_diff_take(dg_engine* e, const dg_merkle* a, const dg_store* sa, const dg_merkle* b,
+                        const dg_store* sb, int side, uint64_t* out_keys, uint64_t cap,
+                        uint64_t* offs, dg_store* rows, uint64_t* n_out, uint64_t* n_total);
+
 /* Same, asynchronous on the engine stream (the loop a replica's anti-entropy timer runs,
  * or several shard diffs in flight): the total goes to d_total[0] (device) and the first
  * min(total, cap) keys to out_keys once the stream reaches them.  Pending asynchronous
